@@ -14,7 +14,12 @@ sample_posterior -> SILoss (interpolant, SiT-XL/2 forward with the 1024-d DINOv2
 cosine alignment) -> backward -> [RCCL gradient all-reduce, overlapped] -> clip_grad_norm_(1.0) -> AdamW -> EMA.
 Global batch 256 is sharded over the N ranks (b = 256/N per GPU, train.py:263); scaling = "strong".
 Rank 0 prints ONE JSON line; `roofline` is the dominant kernel (the bf16 MFMA GEMM) timed live with events on the
-launch stream; `cpu_baseline` is the oracle (CPU restatement, fp32) timed on this box's host cores at N=1.
+launch stream inside the timed steps.
+
+A plain run sets up, warms up, times the steps, writes the outputs of `--dump-outputs DIR` and prints that line, nothing
+more.  `--full` adds, after the timed steps, what takes runs of its own: the isolated GEMM table and attention timing, the
+C3 / C4 / C5 / N2 / N4 legs, the loss-vs-reference leg, the data-parallel diagnosis and `cpu_baseline` (the oracle, a CPU
+restatement in fp32, timed on this box's host cores at N=1); the `--no-*` options drop single parts of it.
 """
 import argparse
 import json
@@ -47,12 +52,17 @@ def parse(argv=None):
                     help="the activation backward (engine.save_act_grad): auto = by tokens per GPU, 1 = saved derivative, 0 = recomputed")
     ap.add_argument("--dgrad-nt", choices=["auto", "0", "1"], default="auto",
                     help="the blocks' input gradients as NT GEMMs on a transposed copy of the weights (engine.dgrad_nt): auto = by tokens per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs, the kernel table, the checks and the CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned (its scalars; a fixed seeded sample of the updated master and EMA "
+                         "weights) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-table", action="store_true")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip the C4 (text + image alignment), C5 (sampler) and N2 (frozen encoder) legs the N = 1 run appends")
-    ap.add_argument("--no-vae-leg", action="store_true", help="skip the SD-VAE decode leg (SURVEY.md N4) the N = 1 run appends")
-    ap.add_argument("--no-loss-vs-ref", action="store_true", help="skip the loss-vs-reference leg (the C2 fixture's 5 injected steps) the N = 1 run appends")
-    ap.add_argument("--no-c3-leg", action="store_true", help="skip the b = 32 per-GPU leg (the 8-GPU shape) the N = 1 run appends")
+    ap.add_argument("--no-config-legs", action="store_true", help="skip the C4 (text + image alignment), C5 (sampler) and N2 (frozen encoder) legs the N = 1 --full run appends")
+    ap.add_argument("--no-vae-leg", action="store_true", help="skip the SD-VAE decode leg (SURVEY.md N4) the N = 1 --full run appends")
+    ap.add_argument("--no-loss-vs-ref", action="store_true", help="skip the loss-vs-reference leg (the C2 fixture's 5 injected steps) the N = 1 --full run appends")
+    ap.add_argument("--no-c3-leg", action="store_true", help="skip the b = 32 per-GPU leg (the 8-GPU shape) the N = 1 --full run appends")
     ap.add_argument("--launch-timeout", type=float, default=2400.0,
                     help="seconds the self-launcher lets its ranks run before it ends them (a hung collective must not hang the caller)")
     ap.add_argument("--tuned-timeout", type=float, default=300.0,
@@ -185,6 +195,24 @@ def random_fill(model, seed):
             a = gain * (3.0 / fan_in) ** 0.5
             v.uniform_(-a, a, generator=g)
     A.shadow_version = -1
+
+
+DUMP_SAMPLE = 1 << 21   # weight elements --dump-outputs writes per arena: 8 MB of fp32 each, far under the 64 MB bound
+
+
+def dump_outputs(out_dir, res, model, ema):
+    """--dump-outputs: what the last timed step handed its caller — its scalars (float64) and, of the fp32 master weights of the
+    model and of the EMA copy that step updated, the same DUMP_SAMPLE elements (float32) drawn with a fixed seed, so that two
+    builds run with the same arguments can be compared output for output.  The optimiser must be flushed first."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in res.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), torch.as_tensor(v).detach().double().reshape(-1).cpu().numpy())
+    n = model._layout.n_train
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(model._arena.master.device)
+    for name, m in (("params_sample", model), ("ema_params_sample", ema)):
+        np.save(os.path.join(out_dir, f"{name}.npy"), m._arena.master[idx].cpu().numpy())
 
 
 # HBM-side bytes per launch of the dominant kernel (the block's grouped weight gradients, b = 256): NOT measured by this run — bench.py
@@ -411,7 +439,7 @@ def c3_leg(step, dev, z_dim, b=32, steps=10, warmup=3, dp_world1=True):
         env = dict(os.environ, REED_FORCE_REDUCER="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29500 + os.getpid() % 2000))
         env["REED_BENCH_TUNED"] = "0"   # one timed region: the plain plan
         cmd = [sys.executable, os.path.abspath(__file__), "--global-batch", str(b), "--steps", str(steps), "--warmup", str(warmup),
-               "--no-cpu-baseline", "--no-kernel-table", "--no-c3-leg", "--no-vae-leg", "--no-config-legs", "--no-loss-vs-ref"]
+               "--full", "--no-cpu-baseline", "--no-kernel-table", "--no-c3-leg", "--no-vae-leg", "--no-config-legs", "--no-loss-vs-ref"]
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -698,6 +726,8 @@ def main():
             return 2.0 * tokens * sum(n * k for n, k in shapes)
         return None
 
+    last_step = {}   # what the last timed step returned (--dump-outputs)
+
     def timed_region(n_warm):
         """n_warm untimed steps, then EXACTLY args.steps steps between barrier + synchronize on both sides; MAX over ranks."""
         res = None
@@ -711,6 +741,7 @@ def main():
             res = step(None, labels, zs, moments=moments)
         barrier()
         dt = time.perf_counter() - t0
+        last_step["res"] = res
         ops.wgrad_group_probe = None
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         if use_dist:
@@ -843,9 +874,15 @@ def main():
     loss_val = chosen["loss"]
     dom = chosen["dom"]
     model.engine().check_errors()
+    if args.dump_outputs:
+        if hasattr(opt, "sync_replicas"):
+            opt.sync_replicas()   # collective: a sharded update leaves each piece of the weights on its owner only
+        opt.flush()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last_step["res"], model, ema)
 
-    # ---- data-parallel diagnosis (after the timed region): bucket plan, bytes, and with a reducer two extra steps with an
-    # event pair around every bucket reduction (comm stream) and around reducer.sync() (compute stream: what the step waits)
+    # ---- data-parallel diagnosis (after the timed region): bucket plan, bytes, and with a reducer and --full two extra steps with
+    # an event pair around every bucket reduction (comm stream) and around reducer.sync() (compute stream: what the step waits)
     L = model._layout
     bk = L.buckets()
     dp = {"world": world, "buckets": len(bk), "gradient_bytes": int(4 * L.n_train),
@@ -855,7 +892,7 @@ def main():
           "tune_error": step.tune_error, "optimizer_sharded": bool(getattr(opt, "_shard", False)),
           "optimizer_shard_tuning": step.shard_tuning,
           "env": {k: v for k, v in os.environ.items() if k.startswith(("REED_", "NCCL_", "RCCL_"))}}
-    if reducer is not None:
+    if reducer is not None and args.full:
         try:
             dp.update(dp_consistency(reducer, opt, model, world, b))
             dp["algo"] = reducer.algo
@@ -911,7 +948,7 @@ def main():
         n_l = sum(len(v) for v in dom.values())
         sag = model.engine().save_act_grad
         sag = b * T_TOK > model.engine().SAVE_ACT_GRAD_MIN_TOKENS if sag is None else sag     # the engine's rule (engine.py)
-        rows = time_gemms(b, D=args_D(model), Hm=model.engine().Hm, act_grad=sag) if not args.no_kernel_table else None
+        rows = time_gemms(b, D=args_D(model), Hm=model.engine().Hm, act_grad=sag) if args.full and not args.no_kernel_table else None
         if n_l or rows is not None:
             if n_l:
                 tot_ms = sum(sum(v) for v in dom.values())
@@ -959,28 +996,29 @@ def main():
                 out["attention"] = time_attention(b)
             except Exception as e:   # a reported leg, never a reason to lose the headline line
                 out["attention"] = {"error": repr(e)}
-        if world == 1 and not args.no_c3_leg and b != 32 and args.model == "SiT-XL/2":
+        legs = world == 1 and args.full   # the legs and the CPU baseline: --full only
+        if legs and not args.no_c3_leg and b != 32 and args.model == "SiT-XL/2":
             try:
                 out["c3_per_gpu_leg"] = c3_leg(step, dev, args.z_dim)
             except Exception as e:   # a reported leg, never a reason to lose the headline line
                 out["c3_per_gpu_leg"] = {"error": repr(e)}
-        if world == 1 and not args.no_config_legs and args.model == "SiT-XL/2":
+        if legs and not args.no_config_legs and args.model == "SiT-XL/2":
             for key, fn in (("c4_per_gpu_leg", c4_leg), ("c5_sampler_leg", c5_leg), ("n2_encoder_leg", n2_encoder_leg)):
                 try:
                     out[key] = fn(dev)
                 except Exception as e:
                     out[key] = {"error": repr(e)}
-        if world == 1 and args.mixed_precision == "bf16" and not args.no_loss_vs_ref:
+        if legs and args.mixed_precision == "bf16" and not args.no_loss_vs_ref:
             try:
                 out["loss_vs_ref"] = loss_vs_ref_leg(dev)
             except Exception as e:
                 out["loss_vs_ref"] = {"error": repr(e)}
-        if world == 1 and not args.no_vae_leg:
+        if legs and not args.no_vae_leg:
             try:
                 out["n4_vae_decode"] = n4_vae_leg(dev)
             except Exception as e:
                 out["n4_vae_decode"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # the baseline is a reported number, never a reason to lose the GPU line

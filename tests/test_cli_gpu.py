@@ -584,10 +584,10 @@ def test_train_with_on_device_jepa_and_mae_towers(dev, tmp_path, monkeypatch):
 
 def test_bench_prints_one_json_line_with_the_contract_keys(dev):
     """bench.py (the driver's entry): exactly one JSON line on stdout with the contract's keys, `roofline` for the dominant kernel
-    timed inside the step, `value` = global batch x steps / measured time, and — in the default form — `cpu_baseline`
+    timed inside the step, `value` = global batch x steps / measured time, and — in the --full form — `cpu_baseline`
     (skipped here for time: its presence is checked through the flag that removes it)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global-batch", "32", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -616,6 +616,36 @@ def test_bench_prints_one_json_line_with_the_contract_keys(dev):
     assert kf["tokens_per_gpu"] == 32 * 256 and kf["activation_backward"].startswith("recomputed") and kf["weight_gradients_on_a_second_stream"] is False
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(dev, tmp_path):
+    """bench.py without --full: the headline line and nothing of the legs, the kernel table or the CPU baseline.  --dump-outputs
+    writes what the last timed step returned (float32 / float64, at most 64 MB), and two runs with the same arguments start from
+    the same inputs: their outputs agree."""
+    recs, dumps = [], []
+    for k in range(2):
+        out_dir = tmp_path / f"out{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "SiT-S/2", "--global-batch", "16", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(out_dir)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        dumps.append({f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))})
+    d = recs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) <= 1e-2 * d["value"]
+    for k in ("cpu_baseline", "c3_per_gpu_leg", "c4_per_gpu_leg", "c5_sampler_leg", "n2_encoder_leg", "loss_vs_ref", "n4_vae_decode",
+              "gemm_family_isolated", "attention"):
+        assert k not in d, k
+    out = dumps[0]
+    assert {"loss.npy", "grad_norm.npy", "params_sample.npy", "ema_params_sample.npy"} <= set(out), sorted(out)
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert abs(float(out["loss.npy"][0]) - d["final_loss"]) <= 1e-5
+    assert sorted(dumps[1]) == sorted(out)
+    for f, a in out.items():
+        np.testing.assert_allclose(dumps[1][f], a, rtol=1e-6, atol=1e-6, err_msg=f)
+
+
 def test_bench_stdout_is_one_line_under_a_reducer(dev):
     """The multi-GPU path of bench.py (process group, RCCL reducer: rehearsed with one rank through REED_FORCE_REDUCER=1): RCCL
     prints a version banner on stdout when the communicator is created — stdout must still be the one JSON line."""
@@ -632,8 +662,8 @@ def test_bench_stdout_is_one_line_under_a_reducer(dev):
 
 def test_bench_self_launch(dev):
     """The driver's command form: `python bench.py --gpus N ...` with NO rank environment.  N = 1 runs in-process and prints one
-    JSON line with the C3 per-GPU leg; N = 2 on this one-GPU box must exit non-zero with a one-line message, promptly (no hang,
-    no rank started)."""
+    JSON line with (--full) the C3 per-GPU leg; N = 2 on this one-GPU box must exit non-zero with a one-line message, promptly (no
+    hang, no rank started)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     bench = os.path.join(ROOT, "bench.py")
     t0 = time.time()
@@ -641,7 +671,7 @@ def test_bench_self_launch(dev):
                        text=True, timeout=120)
     assert r.returncode == 2 and r.stdout.strip() == "" and "only 1 GPU" in r.stderr and time.time() - t0 < 60
     r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "SiT-XL/2", "--global-batch", "64",
-                        "--no-cpu-baseline", "--no-kernel-table", "--no-config-legs", "--no-vae-leg", "--no-loss-vs-ref"], env=env,
+                        "--full", "--no-cpu-baseline", "--no-kernel-table", "--no-config-legs", "--no-vae-leg", "--no-loss-vs-ref"], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

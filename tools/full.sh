@@ -14,6 +14,6 @@ rc=$(cat $O/pytest_rc)
 echo "gpu tests rc=$rc"; tail -4 $O/pytest_gpu.txt
 [ "$rc" != "0" ] && { grep -E "FAILED|Error" $O/pytest_gpu.txt | head -20; exit 1; }
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-echo "bench:"; timeout -k 10 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; rc=$?
+echo "bench:"; timeout -k 10 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; rc=$?
 echo "bench rc=$rc"; cut -c1-400 $O/bench_n1.json
 exit $rc

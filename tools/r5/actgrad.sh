@@ -13,7 +13,7 @@ python -m pytest tests/test_fp32_gpu.py -x -q 2>&1 | tail -3 &&
 for rep in 1 2; do
   for v in 0 1; do
     echo "== b=256 --save-act-grad $v"
-    python bench.py --save-act-grad $v --steps 10 --warmup 3 --no-cpu-baseline --no-config-legs --no-vae-leg --no-loss-vs-ref 2>/dev/null | python -c "
+    python bench.py --save-act-grad $v --steps 10 --warmup 3 --full --no-cpu-baseline --no-config-legs --no-vae-leg --no-loss-vs-ref 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value',d['value'],'ms',d['ms_per_step'],'dom',d['roofline']['avg_ms_per_launch'],'c3',d.get('c3_per_gpu_leg',{}).get('images_per_sec_per_gpu'))

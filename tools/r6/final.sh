@@ -5,6 +5,6 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r6
 mkdir -p $O
 cd $R
-timeout -k 10 700 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || { tail -20 $O/bench_n1.err; exit 1; }
+timeout -k 10 700 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || { tail -20 $O/bench_n1.err; exit 1; }
 cut -c1-400 $O/bench_n1.json
 TAG=r6 timeout -k 10 450 bash tools/profile.sh
