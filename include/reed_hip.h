@@ -135,12 +135,16 @@ int reed_reduce_mod_parts(const float* const* parts, const int64_t* strides, con
  * ------------------------------------------------------------------------------------------- */
 int reed_attention_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, int hd,
                        void* stream);
+/* Backward without a workspace: T <= 256 (the library allocates nothing; longer sequences take the workspace form below). */
 int reed_attention_bwd(const void* qkv, const void* o, const void* d_o, const float* lse,
                        void* dqkv, int B, int T, int H, int hd, void* stream);
 /* The same backward with a caller-owned workspace of reed_attention_bwd_ws_floats(B, T, H) floats (delta = rowsum(dO * O) is
  * formed there by a row kernel, which lets the main kernel run persistently with the next (batch, head) item's operands in
  * flight under the current one: csrc/attention.hip); ws == NULL falls back to reed_attention_bwd.  Replaces the autograd of
- * F.scaled_dot_product_attention inside timm Attention (image/models/sit.py:114-118). */
+ * F.scaled_dot_product_attention inside timm Attention (image/models/sit.py:114-118).
+ * T <= 256, or 256 < T <= 4096 with T % 16 == 0 (512^2 training: T = 1024), anything else is refused.  The workspace is B*T*H
+ * floats for T <= 256; for T > 256 it is B*T*H*(1 + ceil(T/256)*72): delta, then one fp32 partial dQ per 256-key tile, sized for
+ * head_dim 72 because the size function has no head_dim. */
 int64_t reed_attention_bwd_ws_floats(int B, int T, int H);
 int reed_attention_bwd_ws(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, float* ws,
                           int B, int T, int H, int hd, void* stream);

@@ -17,7 +17,8 @@
 // once) with dQ^T = K^T dS^T formed every 64 queries through an LDS tile of dS^T; deterministic, no atomics.  Kernels in
 // this file: attn_fwd_kernel (any T) + attn_fwd_rows_kernel (a <= 16-row tail), attn_fwd256p_kernel (T <= 256, persistent:
 // the engine's forward), attn_bwd_ks_kernel (one shot), attn_bwd_ksp_kernel (persistent, T < 256), attn_bwd_ring_kernel
-// (persistent with Q / dO rings, T = 256: the engine's backward).  Forms that were measured and removed are named where
+// (persistent with Q / dO rings, T = 256: the engine's backward), attn_bwd_long_kernel + attn_dq_reduce_kernel (persistent,
+// 256 < T <= 4096: 512^2 training).  Forms that were measured and removed are named where
 // they stood (round 2's three-barrier forward, round 1's two-phase backward, the half-workgroup stagger).
 #include <stdlib.h>
 
@@ -2334,6 +2335,258 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_ring_kernel(const bf16* __res
 #undef RING_STAMP
 }
 
+// ------------------------------------------------------------------------------------------
+// Backward for 256 < T <= 4096, T % 16 == 0 (512^2 training: T = 1024), persistent.  An item is (batch, head, key tile of 256
+// keys): B H ceil(T / 256) items, dealt to the XCDs in contiguous runs (xcd_contiguous), so the key tiles of one (batch, head),
+// which stream the same Q / dO rows, meet in one L2.  Per item the K tile sits in LDS and a wave owns 32 keys: K / V fragments
+// and the dK / dV accumulators in registers for the whole item, as in attn_bwd_ks_kernel.  The item walks all T queries in
+// 64-query chunks.  A chunk's Q and dO rows and its (log-sum-exp, delta) are loaded into registers one chunk ahead, under the
+// previous chunk's products, and written to LDS at the top of the chunk (the next item's first chunk is fetched under the
+// current item's last one).  Phase A: S, P (recomputed from lse), dP, dS of the wave's keys x the chunk's queries; dK / dV
+// accumulate, dS^T goes to LDS.  Phase B: the chunk's partial dQ^T = K^T dS^T over THIS tile's keys, stored in fp32 to slice kt
+// of the workspace; attn_dq_reduce_kernel sums the ceil(T / 256) slices in tile order and writes the q slot of dqkv.  dK / dV
+// are complete at the end of the item and leave from the MFMA layout (8 bytes per lane).  Deterministic: no atomics, every
+// output element has one owner and a fixed summation order.
+// A last key tile of fewer than 256 keys: rows past T of the K tile are zero, so are their V fragments and dS, phase B stops at
+// the last 32-key block that holds a key, and waves without a key skip phase A.  Queries past T (a last chunk of 16, 32 or 48
+// rows) are zero rows with lse = +inf: p = 0, no contribution; their dQ is not stored.
+// LDS: K | dS^T (256 rows of 144 bytes each) | Q chunk | dO chunk (64 rows + 256 zero bytes, read (x 0) behind the last row by the
+// k-step over columns 64..95 of a 72-wide head) | lse, delta of the chunk = 91 KiB: one workgroup per CU.
+constexpr int LQC = 64 * ROWB + 256;
+constexpr int LONG_LDS = 2 * TILE_B + 2 * LQC + 512;
+
+template <int HD>
+__global__ __launch_bounds__(512, 1) void attn_bwd_long_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o,
+                                                               const float* __restrict__ lse, const float* __restrict__ delta,
+                                                               float* __restrict__ dqp, bf16* __restrict__ dqkv, long slice, int T,
+                                                               int H, int nkt, int nitems) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int KS = Cfg<HD>::KS, DT = Cfg<HD>::DT, NCH = Cfg<HD>::NCH;
+  constexpr int DTA = (DT + 1) / 2;
+  constexpr int NPC = 64 * NCH;                 // 16-byte pieces of one chunk tile
+  constexpr int PER = (2 * NPC + 511) / 512;    // pieces of the Q and dO chunk tiles per thread
+  const int tid0 = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+  const int D = H * HD;
+  const long tok = 3l * D;
+  char* Kt = smem;
+  char* St = smem + TILE_B;     // dS^T[key][query of the chunk], bf16, 64 of a row's 72 columns used
+  char* Qc = smem + 2 * TILE_B;
+  char* Gc = Qc + LQC;
+  float* lse2 = (float*)(Gc + LQC);
+  float* dlt = lse2 + 64;
+  if (tid0 < 16) {
+    *(uint4*)(Qc + 64 * ROWB + tid0 * 16) = make_uint4(0, 0, 0, 0);
+    *(uint4*)(Gc + 64 * ROWB + tid0 * 16) = make_uint4(0, 0, 0, 0);
+  }
+  const float scale = rsqrtf((float)HD);
+  const float sc2 = scale * LOG2E;
+  const int r0 = wave * 32;
+  const int nch = (T + 63) >> 6;
+
+  // a chunk's Q / dO rows -> registers (rows past T clamped here, zeroed by stash); lse (threads 0..63) and delta (64..127)
+  uint4 pre[PER];
+  float pl = 0.f;
+  auto fetch = [&](int item, int ch, int tid) {
+    const int bh = item / nkt, b = bh / H, h = bh - b * H;
+    const bf16* qb = qkv + (long)b * T * tok + h * HD;
+    const bf16* gb = d_o + (long)b * T * D + h * HD;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int idx = min(tid + 512 * k, 2 * NPC - 1);
+      const bool second = idx >= NPC;
+      const int j = second ? idx - NPC : idx;
+      const int row = j / NCH, c = j - row * NCH;
+      const int q = min(ch * 64 + row, T - 1);
+      pre[k] = *(const uint4*)(second ? gb + (long)q * D + c * 8 : qb + (long)q * tok + c * 8);
+    }
+    if (tid < 128) pl = (tid < 64 ? lse : delta)[(long)bh * T + min(ch * 64 + (tid & 63), T - 1)];
+  };
+  auto stash = [&](int ch, int tid) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int idx = tid + 512 * k;
+      if (idx < 2 * NPC) {
+        const bool second = idx >= NPC;
+        const int j = second ? idx - NPC : idx;
+        const int row = j / NCH, c = j - row * NCH;
+        const unsigned msk = ch * 64 + row < T ? 0xFFFFFFFFu : 0u;
+        uint4 w = pre[k];
+        w.x &= msk; w.y &= msk; w.z &= msk; w.w &= msk;
+        *(uint4*)((second ? Gc : Qc) + row * ROWB + c * 16) = w;
+      }
+    }
+    const int q = ch * 64 + (tid & 63);
+    if (tid < 64) lse2[tid] = q < T ? pl * LOG2E : INFINITY;   // queries past T: p = exp2(-inf) = 0
+    else if (tid < 128) dlt[tid - 64] = q < T ? pl : 0.f;
+  };
+
+  int it = xcd_contiguous(blockIdx.x, gridDim.x);
+  if (it < nitems) fetch(it, 0, tid0);
+  for (; it < nitems; it += gridDim.x) {
+    const int bh = it / nkt, kt = it - bh * nkt;
+    const int b = bh / H, h = bh - b * H;
+    const int k0 = kt * 256, kn = min(256, T - k0);
+    const bf16* base = qkv + (long)b * T * tok + h * HD;
+    bf16* dbase = dqkv + (long)b * T * tok + h * HD;
+    float* dqb = dqp + (long)kt * slice + (long)b * T * D + h * HD;
+    int tid = tid0;
+    asm volatile("" : "+v"(tid));   // per-item copy: lane-derived addresses are not hoisted out of the item loop (and spilled)
+    const int lane = tid & 63, i = lane & 15, g = lane >> 4;
+    __syncthreads();   // every wave is done with the previous item's K and dS^T tiles
+    load_tile<HD>(Kt, base + D + (long)k0 * tok, tok, kn, tid, 512);
+    bf16x8 kf[2][KS], vf[2][KS];
+    bool kvalid[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      kvalid[ct] = r0 + 16 * ct + i < kn;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        vf[ct][ks] = load_frag_global<HD>(base + 2 * D + (long)(k0 + min(r0 + 16 * ct + i, kn - 1)) * tok, kvalid[ct], ks, lane);
+    }
+    f32x4 dk[2][DT], dv[2][DT];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) { dk[ct][dt] = zero4(); dv[ct][dt] = zero4(); }
+    const bool active = r0 < kn;           // the wave holds at least one key
+    const int nkb = (kn + 31) >> 5;        // 32-key blocks of the tile that hold a key
+#pragma unroll 1
+    for (int ch = 0; ch < nch; ++ch) {
+      int tc = tid0;
+      asm volatile("" : "+v"(tc));   // the same per chunk
+      const int lane = tc & 63, i = lane & 15, g = lane >> 4;
+      stash(ch, tc);
+      __syncthreads();   // the chunk's rows are in LDS (at ch 0 also the K tile); dS^T is free (phase B of ch - 1 is over)
+      if (ch == 0) {
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) kf[ct][ks] = frag_rows_z<HD>(Kt, r0 + 16 * ct, ks, lane);
+      }
+      {   // the next chunk of this item, or after the last one the first chunk of the next item: one load sequence
+        const bool nx = ch + 1 == nch;
+        const int fi = nx ? it + (int)gridDim.x : it;
+        if (fi < nitems) fetch(fi, nx ? 0 : ch + 1, tc);
+      }
+      // ---------------- phase A: this wave's 32 keys x the chunk's 64 queries ----------------
+      if (active) {
+#pragma unroll 1
+        for (int qh = 0; qh < 2; ++qh) {
+          const int qq0 = qh * 32;
+          f32x4 st[2][2], dp[2][2];  // [qt][ct]: rows q = qq0+16qt+4g+r, col key = r0+16ct+i
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) { st[qt][ct] = zero4(); dp[qt][ct] = zero4(); }
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+              bf16x8 qa = frag_rows(Qc, qq0 + 16 * qt, ks, lane);
+              bf16x8 ga = frag_rows(Gc, qq0 + 16 * qt, ks, lane);
+#pragma unroll
+              for (int ct = 0; ct < 2; ++ct) {
+                st[qt][ct] = MFMA(qa, kf[ct][ks], st[qt][ct]);
+                dp[qt][ct] = MFMA(ga, vf[ct][ks], dp[qt][ct]);
+              }
+            }
+          f32x4 lq4[2], dl4[2];
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt) {
+            lq4[qt] = *(const f32x4*)(lse2 + qq0 + 16 * qt + 4 * g);
+            dl4[qt] = *(const f32x4*)(dlt + qq0 + 16 * qt + 4 * g);
+          }
+          bf16x8 pb[2], dsb[2];
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) {
+            f32x4 p0, p1, s0, s1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              p0[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(st[0][ct][r], sc2, -lq4[0][r]));
+              p1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(st[1][ct][r], sc2, -lq4[1][r]));
+              s0[r] = kvalid[ct] ? p0[r] * (dp[0][ct][r] - dl4[0][r]) : 0.f;   // a key past T contributes nothing to dQ
+              s1[r] = kvalid[ct] ? p1[r] * (dp[1][ct][r] - dl4[1][r]) : 0.f;
+            }
+            pb[ct] = pack2(p0, p1);
+            dsb[ct] = pack2(s0, s1);
+            char* sp = St + (r0 + 16 * ct + i) * ROWB + (qq0 + 4 * g) * 2;
+            *(bf16x4*)sp = __builtin_shufflevector(dsb[ct], dsb[ct], 0, 1, 2, 3);
+            *(bf16x4*)(sp + 32) = __builtin_shufflevector(dsb[ct], dsb[ct], 4, 5, 6, 7);
+          }
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) {
+            bf16x8 gtf = frag_trT(Gc, qq0, 16 * dt, lane);
+            bf16x8 qtf = frag_trT(Qc, qq0, 16 * dt, lane);
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+              dv[ct][dt] = MFMA(gtf, pb[ct], dv[ct][dt]);
+              dk[ct][dt] = MFMA(qtf, dsb[ct], dk[ct][dt]);
+            }
+          }
+        }
+      }
+      __syncthreads();   // dS^T of the chunk is complete; the chunk's Q / dO rows are dead
+      // ---------------- phase B: partial dQ^T = K^T dS^T of the chunk's 64 queries over this tile's keys -> slice kt ----------------
+      {
+        const int qtile = wave >> 1;
+        const int dt0 = (wave & 1) ? DTA : 0;
+        f32x4 dq[DTA];
+#pragma unroll
+        for (int k = 0; k < DTA; ++k) dq[k] = zero4();
+#pragma unroll 1
+        for (int ks = 0; ks < nkb; ++ks) {
+          const bf16x8 dsf = frag_trT(St, 32 * ks, 16 * qtile, lane);
+#pragma unroll
+          for (int k = 0; k < DTA; ++k) {
+            if (dt0 + k < DT) {
+              const bf16x8 ktf = frag_trT(Kt, 32 * ks, 16 * (dt0 + k), lane);
+              dq[k] = MFMA(ktf, dsf, dq[k]);
+            }
+          }
+        }
+        const int q = ch * 64 + 16 * qtile + i;   // rows d = 16 dt + 4 g + r, column q = i: 16 bytes per lane
+#pragma unroll
+        for (int k = 0; k < DTA; ++k) {
+          const int d = 16 * (dt0 + k) + 4 * g;
+          if (dt0 + k < DT && d < HD && q < T) *(f32x4*)(dqb + (long)q * D + d) = dq[k] * scale;
+        }
+      }
+    }
+    // ---------------- dK, dV of the wave's keys: complete, straight from the MFMA layout ----------------
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const int key = k0 + r0 + 16 * ct + i;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        const int d = 16 * dt + 4 * g;
+        if (d < HD && kvalid[ct]) {
+          bf16x4 a, c;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { a[r] = f2bf(dk[ct][dt][r] * scale); c[r] = f2bf(dv[ct][dt][r]); }
+          *(bf16x4*)(dbase + (long)key * tok + D + d) = a;
+          *(bf16x4*)(dbase + (long)key * tok + 2 * D + d) = c;
+        }
+      }
+    }
+  }
+}
+
+// dQ of the long backward: the q slot of dqkv = sum over the nkt slices of dqp (f32 [nkt][B T, D]), in slice order; 4 elements per thread
+__global__ __launch_bounds__(256) void attn_dq_reduce_kernel(const float* __restrict__ dqp, bf16* __restrict__ dqkv, long n4, long slice,
+                                                             int D, int nkt) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n4) return;
+  f32x4 acc = *(const f32x4*)(dqp + 4 * j);
+  for (int kt = 1; kt < nkt; ++kt) acc += *(const f32x4*)(dqp + kt * slice + 4 * j);
+  const long e = 4 * j, tokn = e / D;
+  const int c = (int)(e - tokn * D);
+  bf16x4 v;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = f2bf(acc[r]);
+  *(bf16x4*)(dqkv + tokn * 3 * D + c) = v;
+}
+
 template <typename K>
 int set_lds(K kernel, int bytes) {
   hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -2427,7 +2680,8 @@ extern "C" int reed_attention_bwd(const void* qkv, const void* o, const void* d_
                                   void* dqkv, int B, int T, int H, int hd, void* stream) {
   REED_CHECK_ARG(qkv && o && d_o && lse && dqkv, "attention_bwd: null pointer");
   REED_CHECK_ARG(hd == 64 || hd == 72, "attention: head_dim %d unsupported (64 or 72)", hd);
-  REED_CHECK_ARG(T > 0 && T <= 256, "attention_bwd: T=%d unsupported (training path is T <= 256)", T);
+  REED_CHECK_ARG(T > 0 && T <= 256, "attention_bwd: T=%d unsupported without a workspace (T <= 256; 256 < T <= 4096 runs through "
+                 "reed_attention_bwd_ws / reed_attention_bwd_dp)", T);
   const int lds = 4 * TILE_B + 256 + 2048;
   dim3 grid(B * H);
   // the one-shot key-stationary kernel (S and dP once); the engine's path is reed_attention_bwd_ws / _dp below.  (Round 1's
@@ -2452,15 +2706,21 @@ extern "C" int reed_attention_bwd(const void* qkv, const void* o, const void* d_
 // ------------------------------------------------------------------------------------------
 
 // Backward with a workspace (ws: reed_attention_bwd_ws_floats(B, T, H) floats, caller-owned): delta = rowsum(dO * O) by a row
-// kernel, then the persistent key-stationary kernel (attn_bwd_ring_kernel at T = 256, attn_bwd_ksp_kernel below it).
-extern "C" int64_t reed_attention_bwd_ws_floats(int B, int T, int H) { return (int64_t)B * T * H; }
+// kernel, then the persistent key-stationary kernel (attn_bwd_ring_kernel at T = 256, attn_bwd_ksp_kernel below it,
+// attn_bwd_long_kernel + attn_dq_reduce_kernel above it).  T > 256: delta, then ceil(T / 256) fp32 partial-dQ slices of
+// B T H hd floats each, sized for hd 72 (the signature has no head_dim).
+extern "C" int64_t reed_attention_bwd_ws_floats(int B, int T, int H) {
+  const int64_t n = (int64_t)B * T * H;
+  return T <= 256 ? n : n * (1 + (int64_t)((T + 255) / 256) * 72);
+}
 
 // dpart != NULL: delta comes from the partial dot products of reed_gemm's epilogue 13 (o is not read)
 static int attention_bwd_persistent(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, float* ws,
                                     const float* dpart, int B, int T, int H, int hd, void* stream) {
   REED_CHECK_ARG(qkv && (o || dpart) && d_o && lse && dqkv && ws, "attention_bwd: null pointer");
   REED_CHECK_ARG(hd == 64 || hd == 72, "attention: head_dim %d unsupported (64 or 72)", hd);
-  REED_CHECK_ARG(B > 0 && H > 0 && T > 0 && T <= 256, "attention_bwd: B=%d H=%d T=%d unsupported (training path is T <= 256)", B, H, T);
+  REED_CHECK_ARG(B > 0 && H > 0 && T > 0 && T <= 4096 && (T <= 256 || T % 16 == 0),
+                 "attention_bwd: B=%d H=%d T=%d unsupported (T <= 256, or 256 < T <= 4096 with T a multiple of 16)", B, H, T);
   const int lds = 4 * TILE_B + 256 + 2048;
   const int nitems = B * H;
   const long nseg = (long)B * T * H;
@@ -2495,6 +2755,30 @@ static int attention_bwd_persistent(const void* qkv, const void* o, const void* 
     REED_KLAUNCH(attn_bwd_ksp_kernel<HD>, pgrid, dim3(512), lds, s, (const bf16*)qkv, (const bf16*)d_o, lse, (const float*)ws, \
                  (bf16*)dqkv, T, H, nitems, dbg);                                                                              \
   } while (0)
+  if (T > 256) {
+    // item = (batch, head, 256-key tile); the same grid rules as below (whole XCD rounds, 4 x beside a collective)
+    const int nkt = (T + 255) / 256, litems = B * H * nkt;
+    const dim3 lgrid((unsigned)(litems < gwant ? litems : gwant));
+    const long slice = nseg * hd;
+    float* dqp = ws + nseg;
+#define REED_BWD_LONG(HD)                                                                                                 \
+  do {                                                                                                                    \
+    static int once = set_lds(attn_bwd_long_kernel<HD>, LONG_LDS);                                                        \
+    if (once) return once;                                                                                                \
+    REED_DELTA(HD);                                                                                                       \
+    REED_LAUNCH_CHECK();                                                                                                  \
+    REED_KLAUNCH(attn_bwd_long_kernel<HD>, lgrid, dim3(512), LONG_LDS, s, (const bf16*)qkv, (const bf16*)d_o, lse,         \
+                 (const float*)ws, dqp, (bf16*)dqkv, slice, T, H, nkt, litems);                                            \
+  } while (0)
+    if (hd == 64) REED_BWD_LONG(64);
+    else REED_BWD_LONG(72);
+#undef REED_BWD_LONG
+    REED_LAUNCH_CHECK();
+    const long n4 = slice / 4;
+    REED_KLAUNCH(attn_dq_reduce_kernel, dim3(cdiv(n4, 256)), dim3(256), 0, s, (const float*)dqp, (bf16*)dqkv, n4, slice, H * hd, nkt);
+    REED_LAUNCH_CHECK();
+    return REED_OK;
+  }
   if (T == 256) {
     const int rlds = 4 * 64 * ROWF + 2 * TILE_F + 256 * 128 + 4096;   // 156 KiB
 #define REED_BWD_RING(HD)                                                                                                 \

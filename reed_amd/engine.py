@@ -575,7 +575,7 @@ class Engine:
             # per-head partial dot products with O (12 MB instead of a 302 MB row pass over dO and O at b = 256); where this
             # shape's GEMM kernel has no such epilogue (False, decided once per token count) the plain store + the row kernel
             fused = False
-            if dot_delta.get(dkey, True) and attn_ws is not None and T <= 256:
+            if dot_delta.get(dkey, True) and attn_ws is not None:
                 dpart = f32(M * H * (1 if hd == 64 else 2))
                 fused = dot_delta[dkey] = ops.dgrad_with_head_dots(dy1, self.W(b + "attn.proj.weight"), do, bk.o, dpart, M, D, D, hd,
                                                                    wt=self.WT(b + "attn.proj.weight"))

@@ -398,7 +398,8 @@ def attention_fwd(qkv, o, lse, B, T, H, hd):
 
 def attention_bwd(qkv, o, do, lse, dqkv, B, T, H, hd, ws=None):
     """ws: f32 workspace of attention_bwd_ws_floats(B, T, H) elements -> the persistent backward (delta by a row kernel in
-    front); None -> the workspace-free kernels."""
+    front): T <= 256, or 256 < T <= 4096 with T a multiple of 16 (512^2 training: T = 1024; the workspace then also holds the
+    fp32 partial dQ of every 256-key tile).  None -> the workspace-free kernels: T <= 256 only.  head_dim 64 or 72."""
     if ws is None:
         _call("reed_attention_bwd", _p(qkv), _p(o), _p(do), _p(lse), _p(dqkv), B, T, H, hd, _stream())
     else:
@@ -406,7 +407,8 @@ def attention_bwd(qkv, o, do, lse, dqkv, B, T, H, hd, ws=None):
 
 
 def attention_bwd_dp(qkv, do, lse, dpart, dqkv, ws, B, T, H, hd):
-    """The persistent backward with delta from the partial dot products of gemm epilogue 13 (dpart f32 [H, 1|2, B*T])."""
+    """The persistent backward with delta from the partial dot products of gemm epilogue 13 (dpart f32 [H, 1|2, B*T]); the T range
+    of the ws form above."""
     _call("reed_attention_bwd_dp", _p(qkv), _p(do), _p(lse), _p(dpart), _p(dqkv), _p(ws), B, T, H, hd, _stream())
 
 

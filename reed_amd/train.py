@@ -56,7 +56,8 @@ def parse_args(input_args=None):
     parser.add_argument("--qk-norm", action=argparse.BooleanOptionalAction, default=False)
     # dataset
     parser.add_argument("--data-dir", type=str, default="../data/imagenet256")
-    parser.add_argument("--resolution", type=int, choices=[256], default=256)
+    # 512: latent 64, T = 1024 tokens (the 16-bit attention backward past 256 tokens, csrc/attention.hip:attn_bwd_long_kernel)
+    parser.add_argument("--resolution", type=int, choices=[256, 512], default=256)
     parser.add_argument("--batch-size", type=int, default=256)
     # precision
     parser.add_argument("--allow-tf32", action="store_true")
@@ -113,7 +114,11 @@ def parse_args(input_args=None):
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft checkpoint (diffusers layout): turns on the reference's preview sampling at step 1 "
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
-    return parser.parse_args(input_args) if input_args is not None else parser.parse_args()
+    args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
+    if args.encoder_ckpts and args.resolution != 256:
+        parser.error(f"--encoder-ckpts is built for --resolution 256 only (the on-device encoder towers take 224 / 256-pixel "
+                     f"input); at --resolution {args.resolution} pass --features-dirs, --packed-dir with features, or --synthetic")
+    return args
 
 
 def encoder_specs(enc_type):
@@ -230,7 +235,7 @@ def main(args):
         raise NotImplementedError(
             "this build ships no encoder weights (no network; SURVEY.md §8f N2). Pass --encoder-ckpts <state dict per "
             "clip-vit-* encoder> to run the frozen encoder on the GPU every step, --features-dirs <dir per encoder> with "
-            "precomputed [256,z] features, --synthetic N, or --enc-type None.")
+            "precomputed [T,z] features, --synthetic N, or --enc-type None.")
     if args.features_dirs and len(args.features_dirs) != n_img_enc:
         raise ValueError("--features-dirs needs one directory per --enc-type entry")
 

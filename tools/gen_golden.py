@@ -288,6 +288,27 @@ def g_tiny(ref_sit, ref_loss, ref_samplers):
     save("tiny", **out)
 
 
+def g_tiny512(ref_sit, ref_loss, ref_samplers):
+    """The tiny SiT at 512^2 (latent 64, T = 1024 tokens), fp32, B = 2: hd64 (2 heads of 64) and xl3 (16 heads of 72) — the 16-bit
+    attention backward past 256 tokens (tests/test_train512_gpu.py)."""
+    cases = {
+        "hd64": dict(kw=tiny_kwargs(input_size=64), zspec=[(128, "i")], enc=["dinov2"], co=[1.0]),
+        "xl3": dict(kw=tiny_kwargs(D=1152, heads=16, input_size=64, projector_dim=256), zspec=[(128, "i")], enc=["dinov2"], co=[1.0]),
+    }
+    out = {}
+    for name, c in cases.items():
+        _m, o, total, grads, _ = run_fwd_bwd(ref_sit, ref_loss, c["kw"], 2, 11, c["zspec"], c["enc"], c["co"])
+        out[f"{name}.total"] = total
+        out[f"{name}.denoising_loss"] = o["denoising_loss"]
+        out[f"{name}.proj_loss"] = o["proj_loss"]
+        for k, g in grads.items():
+            out[f"{name}.gnorm.{k}"] = g.double().norm()
+        for k in ("final_layer.linear.weight", "final_layer.linear.bias", "blocks.0.attn.qkv.bias", "x_embedder.proj.weight",
+                  "x_embedder.proj.bias", "blocks.1.adaLN_modulation.1.bias", "blocks.2.mlp.fc1.bias", "projectors.0.4.bias"):
+            out[f"{name}.grad.{k}"] = grads[k]
+    save("tiny512", **out)
+
+
 def g_loss_units(ref_sit, ref_loss, ref_samplers):
     """G-h: SILoss over time_schedule x path_type x weighting with a fixed stand-in model."""
     B = 6
@@ -797,7 +818,7 @@ def g_init(ref_sit, ref_loss, ref_samplers):
     save("init", **out)
 
 
-ALL = {"init": g_init, "static": g_static, "tiny": g_tiny, "loss_units": g_loss_units, "samplers": g_samplers, "optim_toy": g_sched,
+ALL = {"init": g_init, "static": g_static, "tiny": g_tiny, "tiny512": g_tiny512, "loss_units": g_loss_units, "samplers": g_samplers, "optim_toy": g_sched,
        "s2_c1": g_s2, "b2_align": g_b2, "xl2_c2": g_xl, "xl2_c2_gnorms": g_xl_gnorms, "xl2_c4": g_xl_c4, "xl2_infer": g_xl_infer, "samplers_long": g_samplers_long, "samplers_long_xl": g_samplers_long_xl, "fp16": g_fp16, "clip": g_clip, "dataset": g_dataset, "towers": g_towers, "dinov2": g_dinov2}
 
 if __name__ == "__main__":
