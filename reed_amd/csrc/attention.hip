@@ -15,7 +15,7 @@
 //
 // Backward recomputes P from the saved log-sum-exp, key-stationary (a wave owns 32 keys: dK / dV in registers, S and dP
 // once) with dQ^T = K^T dS^T formed every 64 queries through an LDS tile of dS^T; deterministic, no atomics.  Kernels in
-// this file: attn_fwd_kernel (any T) + attn_fwd_rows_kernel (a <= 16-row tail), attn_fwd256p_kernel (T <= 256, persistent:
+// this file: attn_fwd_kernel (any T; <64, true>: a <= 16-row tail past 512 keys) + attn_fwd_rows_kernel (a <= 16-row tail), attn_fwd256p_kernel (T <= 256, persistent:
 // the engine's forward), attn_bwd_ks_kernel (one shot), attn_bwd_ksp_kernel (persistent, T < 256), attn_bwd_ring_kernel
 // (persistent with Q / dO rings, T = 256: the engine's backward), attn_bwd_long_kernel + attn_dq_reduce_kernel (persistent,
 // 256 < T <= 4096: 512^2 training).  Forms that were measured and removed are named where
@@ -155,14 +155,56 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int n) {
 }
 
 // ------------------------------------------------------------------------------------------
+// LDS-DMA tile staging (buffer_load_dwordx4 ... lds): a [256][RB / 16]-chunk tile image is 256 * RB / 1024 wave
+// instructions of 1 KiB; lane L of instruction I carries chunk c = 64 I + L = (row c / CPR, chunk c % CPR) from its own
+// source address to the lane-linear LDS address tile + 16 c.  Chunks behind the head's columns (the pad of a padded row
+// format) and rows >= rows_valid carry an offset outside the descriptor: the hardware range check writes zeros for them,
+// so the tiles need no zero-fill code and ragged T needs no masks on the load side.
+typedef void __attribute__((address_space(3))) * lds_ptr_t;
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int DMA_OOB = 0x7FFFFFF0;
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, long bytes) {
+  if (!base || bytes < 0) bytes = 0;
+  if (bytes > 0x7FFF0000l) bytes = 0x7FFF0000l;
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (unsigned)bytes, 0x00020000);
+}
+template <int HD, int RB>
+__device__ __forceinline__ int dma_voff(int c, int stride_bytes) {
+  constexpr int CPR = RB / 16;
+  const int row = c / CPR, col = c - row * CPR;
+  return col < HD / 8 ? row * stride_bytes + col * 16 : DMA_OOB;
+}
+// bytes of a tile's source window: rows_valid rows of HD elements at stride_bytes
+template <int HD>
+__device__ __forceinline__ long tile_window(int rows_valid, int stride_bytes) {
+  return rows_valid > 0 ? (long)(rows_valid - 1) * stride_bytes + HD * 2 : 0;
+}
+// the lane index computed where it is used (no value to hold across a loop: the compiler cannot hoist a volatile asm)
+__device__ __forceinline__ int lane_here() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+// ------------------------------------------------------------------------------------------
 // Forward for any T (512^2 sampling: T = 1024; the CLIP tower: T = 257): 256-key tiles with online softmax, one
 // workgroup per (batch, head, 256-query block), register-staged tile loads.  T <= 256 runs attn_fwd256p_kernel below.
-template <int HD>
+// TAIL (the DINOv2 towers at 448 px: T = 1025 / 1029): the grid holds the T / 256 full query blocks only, and the last of
+// them also produces the T % 256 <= 16 rows behind it from the K / V tiles it already has in LDS.  Wave w takes output
+// columns 16 (w & 3) .. +15 of those rows over keys 128 (w >> 2) .. +127 of every tile (S^T = K Q_tail^T and
+// O_tail^T += V^T P^T, the layout of the main rows) with an online softmax of its own: 20 MFMAs per tile beside the main
+// rows' 128, in one block per (batch, head).  The four waves of a key half compute the same S^T and softmax: that
+// redundancy buys a 4-VGPR partial O (a 32-key slice per wave would hold a 16-VGPR one across the main rows' loop, which
+// runs at the 128-VGPR budget of two workgroups per CU).  After the last tile the eight partial (m, l, 16 x 16 O) sets meet
+// in the dead V tile and the two key halves are merged in a fixed order (deterministic, no atomics).  The tiles arrive by
+// LDS-DMA (no staging registers), and lane- / wave-dependent offsets are recomputed where used, not held across the loop:
+// with them the instantiation spills nothing (tools/check_attn_tail_isa.py).
+template <int HD, bool TAIL = false>
 __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
                                                        float* __restrict__ lse, int B, int T, int H) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int KS = Cfg<HD>::KS, DT = Cfg<HD>::DT;
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x, lane = tid & 63, tid_in = tid;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
   const int D = H * HD;
@@ -183,13 +225,49 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16* __restrict
   for (int qt = 0; qt < 2; ++qt)
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) ot[qt][dt] = zero4();
+  // TAIL: rows tq0 .. T-1 (MFMA column i = row tq0 + i).  Wave w takes output columns 16 (w & 3) .. +15 of those rows over
+  // keys 128 (w >> 2) .. +127 of every tile: its softmax state (tm, tl) and one 16 x 16 partial O tile
+  static_assert(!TAIL || HD == 64, "the folded tail is built for head_dim 64");
+  const bool tail = TAIL && blockIdx.y == gridDim.y - 1;   // workgroup-uniform
+  const int tq0 = gridDim.y * 256;
+  float tm = -INFINITY, tl = 0.f;
+  f32x4 tot = zero4();
+
+  if constexpr (TAIL) {   // every main row is < T here
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int col = ks * 32 + 8 * g;
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt) qf[qt][ks] = *(const bf16x8*)(base + (long)(q0 + 16 * qt + i) * tok + col);
+    }
+  }
 
   for (int kv0 = 0; kv0 < T; kv0 += 256) {
     __syncthreads();
     const int rows = min(256, T - kv0);
-    load_tile<HD, ROWF>(Kt, base + (long)kv0 * tok + D, tok, rows, tid, 512);
-    load_tile<HD, ROWF>(Vt, base + (long)kv0 * tok + 2 * D, tok, rows, tid, 512);
-    if (kv0 == 0) {  // Q fragments after the first tile loads: keeps the staging registers and Q from overlapping
+    if constexpr (TAIL) {   // by LDS-DMA: no staging registers (the tail's state beside them would not fit in 128 VGPRs)
+      const int tokb = (int)(tok * 2);
+      // the window (rows - 1 rows of stride and one row of HD) is below 2^31 here: no clamp (mk_rsrc's 64-bit clamp holds 2 VGPRs)
+      const unsigned win = (unsigned)((rows - 1) * tokb + HD * 2);
+      const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(base + (long)kv0 * tok + D), 0, win, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(base + (long)kv0 * tok + 2 * D), 0, win,
+                                                                          0x00020000);
+      // the lane's offsets and the wave's LDS pieces are recomputed here for every tile (opaque copies): hoisted out of the
+      // tile loop they would stay live across the main rows' products, 5 VGPRs and 10 SGPRs, and push the kernel into scratch
+      const int ln = lane_here();
+      int wv = wave;
+      asm volatile("" : "+s"(wv));
+#pragma unroll
+      for (int j = 0; j < 5; ++j) {   // this wave's 32 rows of each 160-byte-row tile: five 1-KiB pieces
+        const int vo = dma_voff<HD, ROWF>((wv * 5 + j) * 64 + ln, tokb);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (lds_ptr_t)(Kt + (wv * 5 + j) * 1024), 16, vo, 0, 0, REED_ATTN_LD_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (lds_ptr_t)(Vt + (wv * 5 + j) * 1024), 16, vo, 0, 0, REED_ATTN_LD_AUX);
+      }
+    } else {
+      load_tile<HD, ROWF>(Kt, base + (long)kv0 * tok + D, tok, rows, tid, 512);
+      load_tile<HD, ROWF>(Vt, base + (long)kv0 * tok + 2 * D, tok, rows, tid, 512);
+    }
+    if (!TAIL && kv0 == 0) {  // Q fragments after the first tile loads: keeps the staging registers and Q from overlapping
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         int row = q0 + 16 * qt + i;
@@ -197,8 +275,9 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16* __restrict
         for (int ks = 0; ks < KS; ++ks) qf[qt][ks] = load_frag_global<HD>(base + (long)row * tok, row < T, ks, lane);
       }
     }
+    if constexpr (TAIL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces have landed
     __syncthreads();
-    if (!active) continue;
+    if (!TAIL && !active) continue;   // TAIL: full query blocks only, every wave is active
     const int nsub = (rows + 63) >> 6;
     for (int sub = 0; sub < nsub; ++sub) {
       const int kvs = sub * 64;
@@ -265,11 +344,99 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16* __restrict
           ot[1][dt] = MFMA(vf, pb[1][s], ot[1][dt]);
         }
     }
+    if constexpr (TAIL) {
+      const int kw = (wave >> 2) * 128, dtw = wave & 3;
+      int last = gridDim.y - 1;
+      asm volatile("" : "+s"(last));   // the tail test made here for every tile: a mask held across the loop costs 2 SGPRs
+      if ((int)blockIdx.y == last && kv0 + kw < T) {   // workgroup- / wave-uniform; a key half past a ragged last tile is skipped
+        bf16x8 qtf[KS];   // read again for every tile (an L2 hit), from an address recomputed here: both would spill if hoisted
+        const int ln = lane_here();
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)   // rows past T read row T - 1 (never stored)
+          qtf[ks] = *(const bf16x8*)(base + (long)min(tq0 + (ln & 15), T - 1) * tok + ks * 32 + 8 * (ln >> 4));
+        f32x4 st[8];
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt) {
+          st[kt] = zero4();
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) st[kt] = MFMA(frag_rows_f<false>(Kt, kw + 16 * kt, ks, lane), qtf[ks], st[kt]);
+        }
+        if (kv0 + kw + 128 > T) {
+          asm volatile("; ragged tail key half" ::);
+#pragma unroll
+          for (int kt = 0; kt < 8; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (kv0 + kw + 16 * kt + 4 * g + r >= T) st[kt][r] = -INFINITY;
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) mx = fmaxf(mx, st[kt][r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mnew = fmaxf(tm, mx * sc2);
+        const float alpha = __builtin_amdgcn_exp2f(tm - mnew);
+        tm = mnew;
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 8; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kt][r], sc2, -mnew));
+            st[kt][r] = p;
+            sum += p;
+          }
+        tl = tl * alpha + sum;
+        tot *= alpha;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) tot = MFMA(frag_trT_f(Vt, kw + 32 * s, 16 * dtw, lane), pack2(st[2 * s], st[2 * s + 1]), tot);
+      }
+    }
   }
+  // The epilogue's indices, from copies that the tail instantiation makes opaque: computed at entry and held across the tile
+  // loop they would be spilled there (the tail's state takes the registers they used).  Without TAIL the same values.
+  int bh_ = bh;
+  if constexpr (TAIL) asm volatile("" : "+s"(bh_));
+  {
+  const int tid = TAIL ? wave * 64 + lane_here() : tid_in;
+  const int lane = tid & 63, i = lane & 15, g = lane >> 4;
+  const int b = bh_ / H, h = bh_ % H;
+  const int q0 = blockIdx.y * 256 + wave * 32;
   // O leaves through LDS (the wave's own 32 rows of the K tile, free once every wave is past its last key tile): in the
   // MFMA layout a wave-level store is sixteen 32-byte pieces; staged, it is whole 144-byte row pieces at 16 B per lane.
   __syncthreads();
-  if (!active) return;
+  if constexpr (TAIL) {
+    if (tail) {   // every wave of the tail's workgroup is active (full query blocks only): both barriers are reached by all
+      // per wave: its 16 x 16 O tile unnormalised [row][16], then m and l of the 16 rows, in the dead V tile
+      float* po = (float*)Vt;
+      float* pml = po + 8 * 16 * 16;
+      tl += __shfl_xor(tl, 16, 64);
+      tl += __shfl_xor(tl, 32, 64);
+      *(f32x4*)(po + (wave * 16 + i) * 16 + 4 * g) = tot;
+      if (g == 0) { pml[wave * 32 + i] = tm; pml[wave * 32 + 16 + i] = tl; }
+      __syncthreads();
+      if (tid < 16 * 8) {   // one 8-column piece of one tail row per thread: the key halves of its columns, first half first
+        const int rr = tid >> 3, c = tid & 7, w0 = c >> 1, w1 = 4 + w0;
+        const float m0 = pml[w0 * 32 + rr], m1 = pml[w1 * 32 + rr], mm = fmaxf(m0, m1);
+        const float a0 = __builtin_amdgcn_exp2f(m0 - mm), a1 = __builtin_amdgcn_exp2f(m1 - mm);
+        const float ll = pml[w0 * 32 + 16 + rr] * a0 + pml[w1 * 32 + 16 + rr] * a1;
+        const float* p0 = po + (w0 * 16 + rr) * 16 + 8 * (c & 1);
+        const float* p1 = po + (w1 * 16 + rr) * 16 + 8 * (c & 1);
+        const int q = tq0 + rr;
+        if (q < T) {
+          const float inv = 1.f / ll;
+          bf16x8 v;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] = f2bf((p0[e] * a0 + p1[e] * a1) * inv);
+          *(bf16x8*)(o + ((long)b * T + q) * D + h * HD + 8 * c) = v;
+          if (c == 0 && lse) lse[((long)b * H + h) * T + q] = mm * LN2 + __logf(ll);
+        }
+      }
+    }
+  }
+  if (!TAIL && !active) return;
   char* stg = Kt + (wave * 32) * ROWF;
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
@@ -299,6 +466,7 @@ __global__ __launch_bounds__(512, 4) void attn_fwd_kernel(const bf16* __restrict
       const int rr = qi / NCH, c = qi - rr * NCH;
       if (qi < NQ && q0 + rr < T) *(uint4*)(obase + (long)rr * D + c * 8) = *(const uint4*)(stg + rr * ROWF + c * 16);
     }
+  }
   }
 }
 
@@ -378,32 +546,6 @@ __global__ __launch_bounds__(256) void attn_fwd_rows_kernel(const bf16* __restri
   if (lse && lane == 0) lse[((long)b * H + h) * T + row] = mx + __logf(sum);
 }
 
-// ------------------------------------------------------------------------------------------
-// LDS-DMA tile staging (buffer_load_dwordx4 ... lds): a [256][RB / 16]-chunk tile image is 256 * RB / 1024 wave
-// instructions of 1 KiB; lane L of instruction I carries chunk c = 64 I + L = (row c / CPR, chunk c % CPR) from its own
-// source address to the lane-linear LDS address tile + 16 c.  Chunks behind the head's columns (the pad of a padded row
-// format) and rows >= rows_valid carry an offset outside the descriptor: the hardware range check writes zeros for them,
-// so the tiles need no zero-fill code and ragged T needs no masks on the load side.
-typedef void __attribute__((address_space(3))) * lds_ptr_t;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int DMA_OOB = 0x7FFFFFF0;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mk_rsrc(const void* base, long bytes) {
-  if (!base || bytes < 0) bytes = 0;
-  if (bytes > 0x7FFF0000l) bytes = 0x7FFF0000l;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (unsigned)bytes, 0x00020000);
-}
-template <int HD, int RB>
-__device__ __forceinline__ int dma_voff(int c, int stride_bytes) {
-  constexpr int CPR = RB / 16;
-  const int row = c / CPR, col = c - row * CPR;
-  return col < HD / 8 ? row * stride_bytes + col * 16 : DMA_OOB;
-}
-// bytes of a tile's source window: rows_valid rows of HD elements at stride_bytes
-template <int HD>
-__device__ __forceinline__ long tile_window(int rows_valid, int stride_bytes) {
-  return rows_valid > 0 ? (long)(rows_valid - 1) * stride_bytes + HD * 2 : 0;
-}
 // raw barrier: no compiler-inserted vmcnt(0) (the LDS-DMA of the next tiles stays in flight across it)
 #define ATTN_BARRIER()                                     \
   do {                                                     \
@@ -2654,8 +2796,18 @@ extern "C" int reed_attention_fwd(const void* qkv, void* o, float* lse, int B, i
   }
   const int lds = 2 * TILE_F;
   dim3 grid(B * H, (T + 255) / 256);
-  // a last query block of at most 16 rows (T = 257, 261: the ViT towers) goes to the row kernel
   const int tail = T % 256;
+  // past 512 keys a last query block of at most 16 rows (T = 1025, 1029: the DINOv2 towers at 448 px) rides in the last full
+  // block (attn_fwd_kernel<64, true>)
+  if (hd == 64 && T > 512 && T <= 4096 + 16 && tail >= 1 && tail <= 16) {
+    grid.y = T / 256;
+    static int once = set_lds(attn_fwd_kernel<64, true>, lds);
+    if (once) return once;
+    REED_KLAUNCH((attn_fwd_kernel<64, true>), grid, dim3(512), lds, (hipStream_t)stream, (const bf16*)qkv, (bf16*)o, lse, B, T, H);
+    REED_LAUNCH_CHECK();
+    return REED_OK;
+  }
+  // a last query block of at most 16 rows (T = 257, 261: the ViT towers) goes to the row kernel
   if (hd == 64 && T > 256 && T <= 512 && tail >= 1 && tail <= 16) {
     grid.y = T / 256;
     const int nwaves = B * H * tail;

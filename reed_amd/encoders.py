@@ -369,14 +369,39 @@ def mocov3_key(k):
     return k
 
 
-def load_vit_encoder(enc_type, ckpt_path, device):
+# Why the towers other than DINOv2 do not run at --resolution 512: what the reference itself does with 448 / 512-pixel input
+RESOLUTION_256_ONLY = {
+    "clip": "the reference's CLIP tower adds its 257-row positional_embedding to the 1025 tokens of a 448-pixel image (models/clip_vit.py:218: a shape error)",
+    "mae": "the reference builds MAE with img_size=256, and its patch embedding asserts the input size",
+    "mocov3": "the reference builds MoCo-v3 with img_size=256, and its patch embedding asserts the input size (models/mocov3_vit.py:142)",
+    "jepa": "the reference's I-JEPA path assumes a class token and reshapes 255 rows to (1, 15, 15, dim) (models/jepa.py:474-490), which fails",
+}
+
+
+def vit_resolution_error(enc_type, resolution):
+    """None if the tower of `enc_type` runs at `resolution`, else why not (only DINOv2 is resolution-aware in the reference:
+    utils.py:97-101 resamples its pos_embed to 16 * (resolution // 256) and train.py:62-65 resizes to 224 * (resolution // 256))."""
+    etype = enc_type.split("-")[0]
+    if resolution == 256 or etype.startswith("dinov2"):
+        return None
+    return RESOLUTION_256_ONLY.get(etype, f"no on-device tower for '{enc_type}' at --resolution {resolution}")
+
+
+def load_vit_encoder(enc_type, ckpt_path, device, resolution=256):
     """`jepa-vit-h`, `mocov3-vit-{b,l}`, `mae-vit-l` of image/utils.py:73-82,133-160 from the checkpoint files the reference
     names (ckpts/ijepa_vith.pth: state_dict['encoder'] with a 'module.' prefix; ckpts/mocov3_vit{b,l}.pth: ['state_dict']
     with 'module.base_encoder.' (fix_mocov3_state_dict, utils.py:27-52); ckpts/mae_vitl.pth: ['model']) or a plain state
     dict; `dinov2[reg]-vit-{s,b,l}` of utils.py:92-104 from the torch.hub checkpoint file (dinov2_vit{s,b,l}14[_reg4]_pretrain.pth,
     a plain state dict).  A learned pos_embed of another grid (DINOv2: 37 x 37, MAE: 14 x 14) is resampled to the tower's
-    as utils.py:99-101,140-146 do with timm's resample_abs_pos_embed (bicubic, antialias; a load-time torch call on the CPU)."""
+    as utils.py:99-101,140-146 do with timm's resample_abs_pos_embed (bicubic, antialias; a load-time torch call on the CPU).
+    resolution 512 (DINOv2 only, as in the reference): the tower takes 448-pixel input, 32 x 32 patches (T = 1025 / 1029),
+    and the hub's 37 x 37 pos_embed is resampled to 32 x 32; any other family raises ValueError with the reference's failure."""
+    why = vit_resolution_error(enc_type, resolution)
+    if why:
+        raise ValueError(f"{enc_type} at resolution {resolution}: {why}")
     cfg = VIT_TOWERS[enc_type]
+    if resolution != 256:
+        cfg = dict(cfg, image=224 * (resolution // 256))
     enc = VitEncoder(**cfg)
     sd = torch.load(ckpt_path, map_location="cpu")
     for key in ("encoder", "state_dict", "model"):

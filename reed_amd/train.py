@@ -15,8 +15,9 @@ sampling at step 1 / every --sampling-steps runs only with --vae-ckpt (a local S
 PNG grids instead of wandb images (§9-2); checkpoints and
 args.json are written regardless of --report-to (§9-11); gradients are clipped once and the pre-clip norm is
 logged (§9-5); unknown --text-embeds-dir names get their width from the first .npy (§9-9).
-Additive flags: --features-dirs (precomputed frozen-encoder features, §8f N2), --encoder-ckpts (clip-vit-* encoder run
-on the GPU every step from a user-supplied state dict, reed_amd/encoders.py), --synthetic N (random latents),
+Additive flags: --features-dirs (precomputed frozen-encoder features, §8f N2), --encoder-ckpts (frozen image encoders run
+on the GPU every step from user-supplied state dicts, reed_amd/encoders.py; at --resolution 512 the dinov2[reg]-vit-* towers
+only, at 448 pixels as the reference runs them), --synthetic N (random latents),
 --log-every.
 """
 import argparse
@@ -101,7 +102,8 @@ def parse_args(input_args=None):
                         help="precomputed frozen-encoder features, one dir per --enc-type entry")
     parser.add_argument("--encoder-ckpts", type=str, nargs="*", default=None,
                         help="state dicts of the frozen image encoders, one per --enc-type entry: the encoder runs on the "
-                             "GPU every step as in the reference (clip-vit-* only: reed_amd/encoders.py, SURVEY.md §8f N2)")
+                             "GPU every step as in the reference (CLIP, DINOv2, I-JEPA, MoCo-v3, MAE towers: reed_amd/encoders.py, SURVEY.md §8f N2; "
+                             "at --resolution 512 dinov2[reg]-vit-* only)")
     parser.add_argument("--packed-dir", type=str, default=None,
                         help="train from a directory written by `python -m reed_amd.dataset pack` (memory-mapped arrays of "
                              "the same items as --data-dir, SURVEY.md §8f N3)")
@@ -116,8 +118,14 @@ def parse_args(input_args=None):
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
     if args.encoder_ckpts and args.resolution != 256:
-        parser.error(f"--encoder-ckpts is built for --resolution 256 only (the on-device encoder towers take 224 / 256-pixel "
-                     f"input); at --resolution {args.resolution} pass --features-dirs, --packed-dir with features, or --synthetic")
+        from .encoders import vit_resolution_error
+        items = [] if args.enc_type in (None, "None") else args.enc_type.split(",")
+        why = [f"{item}: {vit_resolution_error(item, args.resolution)}" for item in items
+               if vit_resolution_error(item, args.resolution)]
+        if why:
+            parser.error(f"--encoder-ckpts is built for --resolution 256 only for every tower but dinov2[reg]-vit-* (the DINOv2 "
+                         f"towers run at 448 pixels); {'; '.join(why)}. At --resolution {args.resolution} pass --features-dirs, "
+                         f"--packed-dir with features, or --synthetic")
     return args
 
 
@@ -226,7 +234,7 @@ def main(args):
             if etype == "clip":
                 encoders.append(load_clip_encoder(cfg[0].upper(), path, device))
             elif key in VIT_TOWERS:
-                encoders.append(load_vit_encoder(key, path, device))
+                encoders.append(load_vit_encoder(key, path, device, resolution=args.resolution))
             else:
                 raise NotImplementedError(f"on-device frozen encoder '{item}': built are clip-vit-*, {sorted(VIT_TOWERS)} (the "
                                           "towers image/utils.py:55-164 defines, configures or fetches; for others use "

@@ -740,6 +740,55 @@ def g_dinov2(ref_sit, ref_loss, ref_samplers):
     save("dinov2", **out)
 
 
+def g_dinov2_512(ref_sit, ref_loss, ref_samplers):
+    """DINOv2 at --resolution 512 (utils.py:97-101, train.py:62-65): the towers see 448-pixel input, 32 x 32 patches + class token
+    (+ 4 registers) = T 1025 / 1029, with the hub's 37 x 37 pos_embed resampled to 32 x 32 (bicubic, antialias).  The same
+    independent port as g_dinov2 (transformers' Dinov2Model / Dinov2WithRegistersModel) at image_size 448; its own position table
+    is the resampled one (the tests rebuild it from the same seed); pos_resample32 is that geometry on a 16-wide table.  Patch tokens sub-sampled along tokens ([:, ::8] / [:, ::16]) to stay small."""
+    from transformers import Dinov2Config, Dinov2Model, Dinov2WithRegistersConfig, Dinov2WithRegistersModel
+    from oracle import vit_towers as ot
+    out = {}
+    for tag, E, H, depth, reg, B, step in (("plain", 128, 2, 2, 0, 2, 8), ("reg4", 256, 4, 2, 4, 2, 16)):
+        cfg = ot.make_config(E, depth, H, 14, 448, True, True, "learned", ls=True, reg=reg)
+        P = ot.fill_params(cfg, base_seed=21)
+        pe = detfill.normal((1, 1 + 37 * 37, E), 58 + reg) * 0.5
+        g = pe[:, 1:].reshape(1, 37, 37, E).permute(0, 3, 1, 2)
+        g = torch.nn.functional.interpolate(g, size=(32, 32), mode="bicubic", antialias=True).permute(0, 2, 3, 1).reshape(1, 1024, E)
+        P["pos_embed"] = torch.cat([pe[:, :1], g], 1)
+        kw = dict(hidden_size=E, num_hidden_layers=depth, num_attention_heads=H, mlp_ratio=4, image_size=448, patch_size=14,
+                  layer_norm_eps=1e-6, qkv_bias=True, hidden_act="gelu", use_swiglu_ffn=False)
+        m = (Dinov2WithRegistersModel(Dinov2WithRegistersConfig(num_register_tokens=reg, **kw)) if reg
+             else Dinov2Model(Dinov2Config(**kw)))
+        sd = {"embeddings.cls_token": P["cls_token"], "embeddings.mask_token": torch.zeros(1, E),
+              "embeddings.position_embeddings": P["pos_embed"],
+              "embeddings.patch_embeddings.projection.weight": P["patch_embed.proj.weight"],
+              "embeddings.patch_embeddings.projection.bias": P["patch_embed.proj.bias"],
+              "layernorm.weight": P["norm.weight"], "layernorm.bias": P["norm.bias"]}
+        if reg:
+            sd["embeddings.register_tokens"] = P["register_tokens"]
+        for i in range(depth):
+            b, h = f"blocks.{i}.", f"encoder.layer.{i}."
+            for j, nm in enumerate(("query", "key", "value")):
+                sd[h + f"attention.attention.{nm}.weight"] = P[b + "attn.qkv.weight"][j * E:(j + 1) * E]
+                sd[h + f"attention.attention.{nm}.bias"] = P[b + "attn.qkv.bias"][j * E:(j + 1) * E]
+            for src, dst in (("norm1", "norm1"), ("norm2", "norm2"), ("attn.proj", "attention.output.dense"), ("mlp.fc1", "mlp.fc1"),
+                             ("mlp.fc2", "mlp.fc2")):
+                sd[h + dst + ".weight"], sd[h + dst + ".bias"] = P[b + src + ".weight"], P[b + src + ".bias"]
+            sd[h + "layer_scale1.lambda1"], sd[h + "layer_scale2.lambda1"] = P[b + "ls1.gamma"], P[b + "ls2.gamma"]
+        m.load_state_dict(sd, strict=True)
+        m.eval()
+        x = detfill.normal((B, 3, 448, 448), 59)
+        with torch.no_grad():
+            out[tag + ".fp32"] = m(pixel_values=x).last_hidden_state[:, 1 + reg::step].numpy()
+            with torch.autocast("cpu", dtype=torch.bfloat16):
+                out[tag + ".bf16"] = m(pixel_values=x).last_hidden_state[:, 1 + reg::step].float().numpy()
+    pe = detfill.normal((1, 1 + 37 * 37, 16), 60)   # the loader's 37 x 37 -> 32 x 32 geometry on a narrow fixed table
+    g = pe[:, 1:].reshape(1, 37, 37, 16).permute(0, 3, 1, 2)
+    g = torch.nn.functional.interpolate(g, size=(32, 32), mode="bicubic", antialias=True).permute(0, 2, 3, 1).reshape(1, 1024, 16)
+    out["pos_resample32"] = torch.cat([pe[:, :1], g], 1).numpy()
+    save("dinov2_512", **out)
+
+
 def make_tiny_dataset(root, n=6, text_dim=16):
     """Deterministic tiny dataset in the reference's on-disk format (image/dataset.py:18-85; written by
     preprocessing/dataset_tools.py): images/XXXXX/imgNNNNNNNN.png, vae-sd/XXXXX/img-mean-std-NNNNNNNN.npy,
@@ -819,7 +868,8 @@ def g_init(ref_sit, ref_loss, ref_samplers):
 
 
 ALL = {"init": g_init, "static": g_static, "tiny": g_tiny, "tiny512": g_tiny512, "loss_units": g_loss_units, "samplers": g_samplers, "optim_toy": g_sched,
-       "s2_c1": g_s2, "b2_align": g_b2, "xl2_c2": g_xl, "xl2_c2_gnorms": g_xl_gnorms, "xl2_c4": g_xl_c4, "xl2_infer": g_xl_infer, "samplers_long": g_samplers_long, "samplers_long_xl": g_samplers_long_xl, "fp16": g_fp16, "clip": g_clip, "dataset": g_dataset, "towers": g_towers, "dinov2": g_dinov2}
+       "s2_c1": g_s2, "b2_align": g_b2, "xl2_c2": g_xl, "xl2_c2_gnorms": g_xl_gnorms, "xl2_c4": g_xl_c4, "xl2_infer": g_xl_infer, "samplers_long": g_samplers_long, "samplers_long_xl": g_samplers_long_xl, "fp16": g_fp16, "clip": g_clip, "dataset": g_dataset, "towers": g_towers, "dinov2": g_dinov2,
+       "dinov2_512": g_dinov2_512}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
