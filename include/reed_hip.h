@@ -352,6 +352,25 @@ int reed_conv3x3(const void* a, const void* w, const float* bias, float* out, in
 /* p (operand type) [rows, ldp] = softmax over the first `cols` columns of scale * s f32 [rows, lds] */
 int reed_softmax_rows(const float* s, int64_t lds, void* p, int64_t ldp, int rows, int cols, float scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SD-VAE encoder (`python -m reed_amd.dataset encode`; the reference's image/preprocessing/dataset_tools.py encode through
+ * diffusers' AutoencoderKL.encode: reed_amd/vae.py restates it).  The same ResNet / attention passes as the decoder plus:
+ * ------------------------------------------------------------------------------------------- */
+/* 3x3 convolution at stride 2 with zero padding of one row at the bottom and one column at the right only (diffusers'
+ * Downsample2D(padding=0): F.pad(x, (0, 1, 0, 1)), then the convolution): out f32 [B * (Hi / 2) * (Wi / 2), ldc] (+)= conv(a) + bias,
+ * tap (ky, kx) of output (y, x) reads a(b, 2y + ky, 2x + kx), zero at or beyond Hi / Wi (odd sizes included).  Arguments as
+ * reed_conv3x3; Hi, Wi >= 2. */
+int reed_conv3x3_down(const void* a, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi, int C, int N,
+                      int accumulate, void* stream);
+/* conv_in's row operand from the dataset's pixels: raw u8 [B, 3, H, W] -> out (operand type) [nrows, ldo], row r - row0 = position
+ * r = (b, y, x) of [B, H, W], column tap * 3 + c = raw(b, c, y + tap / 3 - 1, x + tap % 3 - 1) / 127.5 - 1, 0 outside the image
+ * (padding in the normalised domain), columns [27, kcols) zero.  kcols >= 28, kcols and ldo multiples of 4. */
+int reed_vae_image_rows(const uint8_t* raw, int B, int H, int W, int64_t row0, int64_t nrows, int kcols, void* out, int64_t ldo,
+                        void* stream);
+/* The encoder's tail after conv_out: y f32 [B*h*w, ldc] (first 8 columns) -> z = quant_conv(y) (qw f32 [8, 8] as [out, in], qb f32
+ * [8], fp32), mean = z[0:4], std = exp(clamp(z[4:8], -30, 20) / 2); out f32 [B, 8, h, w] = cat[mean, std] (NCHW). */
+int reed_vae_moments(const float* y, int64_t ldc, int B, int h, int w, const float* qw, const float* qb, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 // Tile 128 x 128 x 64, four waves of 64 x 64 (v_mfma_f32_16x16x32), two workgroups per CU, LDS double buffered — the structure
 // of gemm.hip's kernel; the epilogue goes through the wave's LDS patch so that every global access is row-contiguous, adds the
 // fp32 bias and, with `accumulate`, the fp32 residual already in `out` (the ResNet block's skip connection, in place).
+// reed_conv3x3_down is the same kernel at stride 2 with diffusers' (0, 1, 0, 1) zero padding: the SD-VAE encoder's downsamplers.
 #include "gemm_common.hpp"
 
 namespace {
@@ -31,6 +32,10 @@ struct ConvArgs {
   int M, N, C, Hi, Wi, up, accumulate;
 };
 
+// DOWN: the stride-2 form (reed_conv3x3_down; a.up == 0): output (y, x) of the [Hi / 2, Wi / 2] grid, tap (ky, kx) reads input
+// (2y + ky, 2x + kx), zero at or beyond Hi / Wi (diffusers' Downsample2D: F.pad(x, (0, 1, 0, 1)), then the 3x3 convolution at
+// stride 2).  Only the per-lane gather offset differs; DOWN = false is the padding-1 kernel above.
+template <bool DOWN>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -53,9 +58,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
   const int tn = (bid % per_group) / gs;
   const int m0 = tm * BM, n0 = tn * BN;
   const int K = 9 * a.C, nt = K / BK;
-  const int Ho = a.Hi << a.up, Wo = a.Wi << a.up;
+  const int Ho = DOWN ? a.Hi >> 1 : a.Hi << a.up, Wo = DOWN ? a.Wi >> 1 : a.Wi << a.up;
 
-  const long abytes = (long)(a.M >> (2 * a.up)) * a.C * 2;        // B * Hi * Wi * C operand elements
+  const long abytes = DOWN ? (long)(a.M / (Ho * Wo)) * a.Hi * a.Wi * a.C * 2     // B * Hi * Wi * C operand elements
+                           : (long)(a.M >> (2 * a.up)) * a.C * 2;
   const __amdgpu_buffer_rsrc_t rsA = make_rsrc(a.a, abytes);
   const __amdgpu_buffer_rsrc_t rsW = make_rsrc(a.w + (long)n0 * K, (long)(a.N - n0) * K * 2);
 
@@ -67,6 +73,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
     const int b = m / (Ho * Wo), rem = m - b * (Ho * Wo);
     py[i] = m < a.M ? rem / Wo : -4;                              // a row beyond M: every tap lands outside the image
     px[i] = rem - (rem / Wo) * Wo;
+    if (DOWN) {                                                   // the window's top-left input pixel
+      py[i] *= 2;
+      px[i] *= 2;
+    }
     pb[i] = b * a.Hi * a.Wi;
   }
   const int cchunk = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;          // stage_row's swizzle: chunk (tid & 7) of row r holds k-chunk c
@@ -76,12 +86,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
     char* tq = tp + TILE_BYTES;
     const int k0 = t * BK;
     const int tap = k0 / a.C, cb = k0 - tap * a.C;
-    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+    const int dy = tap / 3 - (DOWN ? 0 : 1), dx = tap - (tap / 3) * 3 - (DOWN ? 0 : 1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int yy = py[i] + dy, xx = px[i] + dx;
-      const bool in = (unsigned)yy < (unsigned)Ho && (unsigned)xx < (unsigned)Wo;
-      const int pix = pb[i] + (yy >> a.up) * a.Wi + (xx >> a.up);
+      const bool in = DOWN ? (unsigned)yy < (unsigned)a.Hi && (unsigned)xx < (unsigned)a.Wi
+                           : (unsigned)yy < (unsigned)Ho && (unsigned)xx < (unsigned)Wo;
+      const int pix = DOWN ? pb[i] + yy * a.Wi + xx : pb[i] + (yy >> a.up) * a.Wi + (xx >> a.up);
       const int voff = in ? (pix * a.C + cb + cchunk) * 2 : 0x7FFFFFF0;
       char* dst = tp + (i * 256 + wave * 64) * 16;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
@@ -168,6 +179,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvArgs a) {
   }
 }
 
+template <bool DOWN>
+int launch_conv(const ConvArgs& ca, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)conv3x3_kernel<DOWN>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
+    attr_set = true;
+  }
+  const int ntm = cdiv(ca.M, BM), ntn = ca.N / BN;
+  REED_KLAUNCH(conv3x3_kernel<DOWN>, dim3(ntm * ntn), dim3(256), 2 * STAGE_BYTES, stream, ca);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
 }  // namespace
 
 extern "C" int reed_conv3x3(const void* a, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi, int C,
@@ -181,14 +205,20 @@ extern "C" int reed_conv3x3(const void* a, const void* w, const float* bias, flo
                  "reed_conv3x3: the activation must stay below 2 GiB (32-bit DMA offsets): decode fewer images per call");
   REED_CHECK_ARG(((uintptr_t)a % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 16) == 0 && (!bias || (uintptr_t)bias % 16 == 0),
                  "reed_conv3x3: operands must be 16-byte aligned");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv3x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-    attr_set = true;
-  }
   ConvArgs ca{(const bf16*)a, (const bf16*)w, bias, out, (long)ldc, (int)M, N, C, Hi, Wi, upsample, accumulate};
-  const int ntm = cdiv(M, BM), ntn = N / BN;
-  REED_KLAUNCH(conv3x3_kernel, dim3(ntm * ntn), dim3(256), 2 * STAGE_BYTES, (hipStream_t)stream, ca);
-  REED_LAUNCH_CHECK();
-  return REED_OK;
+  return launch_conv<false>(ca, (hipStream_t)stream);
+}
+
+extern "C" int reed_conv3x3_down(const void* a, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi,
+                                 int C, int N, int accumulate, void* stream) {
+  REED_CHECK_ARG(B > 0 && Hi > 1 && Wi > 1 && C > 0 && N > 0, "reed_conv3x3_down: empty problem (Hi, Wi >= 2)");
+  REED_CHECK_ARG(C % 64 == 0 && N % 128 == 0, "reed_conv3x3_down: C=%d must be a multiple of 64 and N=%d of 128", C, N);
+  REED_CHECK_ARG(ldc >= N && ldc % 4 == 0 && ldc < (1 << 20), "reed_conv3x3_down: ldc=%ld", (long)ldc);
+  const long M = (long)B * (Hi >> 1) * (Wi >> 1);
+  REED_CHECK_ARG((long)B * Hi * Wi * C * 2 <= 0x7FFF0000l && M < (1l << 31) - 128,
+                 "reed_conv3x3_down: the activation must stay below 2 GiB (32-bit DMA offsets): encode fewer images per call");
+  REED_CHECK_ARG(((uintptr_t)a % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 16) == 0 && (!bias || (uintptr_t)bias % 16 == 0),
+                 "reed_conv3x3_down: operands must be 16-byte aligned");
+  ConvArgs ca{(const bf16*)a, (const bf16*)w, bias, out, (long)ldc, (int)M, N, C, Hi, Wi, 0, accumulate};
+  return launch_conv<true>(ca, (hipStream_t)stream);
 }

@@ -107,9 +107,11 @@ __device__ __forceinline__ float act_fwd(int epi, int variant, float x) {
 
 // C > 0 (NT only): P is not a matrix but the 3x3 window gather of an NHWC activation a.P f32 [B, Hi, Wi, C] — row m = output pixel
 // (b, y, x) of the [B, Hi << up, Wi << up] grid, column k = tap * C + c = a(b, (y + tap / 3 - 1) >> up, (x + tap % 3 - 1) >> up, c),
-// zero outside the grid: the convolutions of the SD-VAE decoder (reed_conv3x3) without an im2col matrix.  C == 0: a plain GEMM.
+// zero outside the grid: the convolutions of the SD-VAE decoder (reed_conv3x3) without an im2col matrix.  down = 1 (up = 0): the
+// stride-2 form of the SD-VAE encoder's downsamplers (reed_conv3x3_down), row m = output pixel (b, y, x) of [B, Hi / 2, Wi / 2],
+// column k = a(b, 2y + tap / 3, 2x + tap % 3, c), zero at or beyond Hi / Wi.  C == 0: a plain GEMM.
 struct ConvGeo {
-  int C, Hi, Wi, up;
+  int C, Hi, Wi, up, down;
 };
 
 template <int LAY, int W>
@@ -145,13 +147,13 @@ __global__ __launch_bounds__(64 * W * W, W == 2 ? 2 : 1) void gemm_f32_kernel(Ge
   // window gather: the output pixel of each of this thread's row pieces, decomposed once
   int cy[Geo<W>::PP], cx[Geo<W>::PP], cb[Geo<W>::PP];
   if (LAY == LAY_NT && cg.C > 0) {
-    const int Ho = cg.Hi << cg.up, Wo = cg.Wi << cg.up;
+    const int Ho = cg.down ? cg.Hi >> 1 : cg.Hi << cg.up, Wo = cg.down ? cg.Wi >> 1 : cg.Wi << cg.up;
 #pragma unroll
     for (int i = 0; i < Geo<W>::PP; ++i) {
       const int m = m0 + ((tid + i * Geo<W>::NT) >> 2);
       const int b = m / (Ho * Wo), rem = m - b * (Ho * Wo);
-      cy[i] = m < a.M ? rem / Wo : -4;          // a row beyond M: every tap lands outside
-      cx[i] = rem - (rem / Wo) * Wo;
+      cy[i] = (m < a.M ? rem / Wo : -4) * (1 + cg.down);   // a row beyond M: every tap lands outside
+      cx[i] = (rem - (rem / Wo) * Wo) * (1 + cg.down);
       cb[i] = b * cg.Hi * cg.Wi;
     }
   }
@@ -159,13 +161,13 @@ __global__ __launch_bounds__(64 * W * W, W == 2 ? 2 : 1) void gemm_f32_kernel(Ge
     const int k0 = kbeg + t * BK;
     if constexpr (LAY == LAY_TN) load_tr<W>(sp, a.P, a.ldp, m0, a.M, k0, kend, tid);
     else if (LAY == LAY_NT && cg.C > 0) {
-      const int Ho = cg.Hi << cg.up, Wo = cg.Wi << cg.up;
+      const int Hg = cg.Hi << cg.up, Wg = cg.Wi << cg.up, pad = 1 - cg.down;   // the grid the taps index, its top / left pad
 #pragma unroll
       for (int i = 0; i < Geo<W>::PP; ++i) {
         const int k = k0 + ((tid + i * Geo<W>::NT) & 3) * 4;
         const int tap = k / cg.C, c = k - tap * cg.C;
-        const int yy = cy[i] + tap / 3 - 1, xx = cx[i] + (tap - (tap / 3) * 3) - 1;
-        const bool in = k < kend && (unsigned)yy < (unsigned)Ho && (unsigned)xx < (unsigned)Wo;
+        const int yy = cy[i] + tap / 3 - pad, xx = cx[i] + (tap - (tap / 3) * 3) - pad;
+        const bool in = k < kend && (unsigned)yy < (unsigned)Hg && (unsigned)xx < (unsigned)Wg;
         sp.v[i] = in ? *(const f32x4*)(a.P + ((long)(cb[i] + (yy >> cg.up) * cg.Wi + (xx >> cg.up)) * cg.C + c))
                      : f32x4{0.f, 0.f, 0.f, 0.f};
       }
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(64 * W * W, W == 2 ? 2 : 1) void gemm_f32_kernel(Ge
 }
 
 template <int LAY, int W>
-int launch_w(const GemmArgs& a, int epi, int splits, hipStream_t stream, ConvGeo cg = ConvGeo{0, 0, 0, 0}) {
+int launch_w(const GemmArgs& a, int epi, int splits, hipStream_t stream, ConvGeo cg = ConvGeo{0, 0, 0, 0, 0}) {
   constexpr int lds = 2 * 2 * Geo<W>::TILE_FLOATS * (int)sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -332,15 +334,15 @@ extern "C" int reed_wgrad_group_deal(int, const int*, const int*, const int*, in
 
 // 3x3 convolution, padding 1, optional nearest x2 upsampling of the input, as an implicit GEMM on the fp32 MFMA kernel above (the
 // 16-bit builds have their own: conv.hip): out f32 [B*Ho*Wo, ldc] (+)= conv(a f32 NHWC [B, Hi, Wi, C]; w f32 [N, 9 C]) + bias.
-extern "C" int reed_conv3x3(const void* act, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi, int C,
-                            int N, int upsample, int accumulate, void* stream) {
-  REED_CHECK_ARG(act && w && out && B > 0 && Hi > 0 && Wi > 0 && C > 0 && N > 0, "reed_conv3x3: empty problem");
-  REED_CHECK_ARG(upsample == 0 || upsample == 1, "reed_conv3x3: upsample must be 0 or 1 (nearest x2)");
-  REED_CHECK_ARG(C % 4 == 0 && N % 4 == 0 && ldc >= N, "reed_conv3x3(fp32): C=%d and N=%d must be multiples of 4, ldc >= N", C, N);
-  const long M = (long)B * (Hi << upsample) * (Wi << upsample);
-  REED_CHECK_ARG(M < (1l << 31) - 256 && (long)B * Hi * Wi < (1l << 31), "reed_conv3x3: too many positions for one call");
+static int conv3x3_f32(const char* what, const void* act, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi,
+                       int Wi, int C, int N, int upsample, int down, int accumulate, void* stream) {
+  REED_CHECK_ARG(act && w && out && B > 0 && Hi > down && Wi > down && C > 0 && N > 0, "%s: empty problem", what);
+  REED_CHECK_ARG(upsample == 0 || upsample == 1, "%s: upsample must be 0 or 1 (nearest x2)", what);
+  REED_CHECK_ARG(C % 4 == 0 && N % 4 == 0 && ldc >= N, "%s(fp32): C=%d and N=%d must be multiples of 4, ldc >= N", what, C, N);
+  const long M = down ? (long)B * (Hi >> 1) * (Wi >> 1) : (long)B * (Hi << upsample) * (Wi << upsample);
+  REED_CHECK_ARG(M < (1l << 31) - 256 && (long)B * Hi * Wi < (1l << 31), "%s: too many positions for one call", what);
   REED_CHECK_ARG(((uintptr_t)act % 16) == 0 && ((uintptr_t)w % 16) == 0 && (!bias || (uintptr_t)bias % 16 == 0),
-                 "reed_conv3x3: operands must be 16-byte aligned");
+                 "%s: operands must be 16-byte aligned", what);
   GemmArgs a;
   memset(&a, 0, sizeof(a));
   a.P = (const float*)act;
@@ -356,7 +358,19 @@ extern "C" int reed_conv3x3(const void* act, const void* w, const float* bias, f
   a.accumulate = accumulate;
   a.rows_per_gate = 1;
   a.ksplit_len = a.K;
-  return launch_w<LAY_NT, 2>(a, EPI_F32, 1, (hipStream_t)stream, ConvGeo{C, Hi, Wi, upsample});
+  return launch_w<LAY_NT, 2>(a, EPI_F32, 1, (hipStream_t)stream, ConvGeo{C, Hi, Wi, upsample, down});
+}
+
+extern "C" int reed_conv3x3(const void* act, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi, int C,
+                            int N, int upsample, int accumulate, void* stream) {
+  return conv3x3_f32("reed_conv3x3", act, w, bias, out, ldc, B, Hi, Wi, C, N, upsample, 0, accumulate, stream);
+}
+
+// the stride-2 form with diffusers' (0, 1, 0, 1) padding (the SD-VAE encoder's downsamplers): out [B * (Hi / 2) * (Wi / 2), ldc]
+extern "C" int reed_conv3x3_down(const void* act, const void* w, const float* bias, float* out, int64_t ldc, int B, int Hi, int Wi,
+                                 int C, int N, int accumulate, void* stream) {
+  REED_CHECK_ARG(Hi > 1 && Wi > 1, "reed_conv3x3_down: Hi=%d, Wi=%d must be at least 2", Hi, Wi);
+  return conv3x3_f32("reed_conv3x3_down", act, w, bias, out, ldc, B, Hi, Wi, C, N, 0, 1, accumulate, stream);
 }
 
 int reed_gemm_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t stream) {

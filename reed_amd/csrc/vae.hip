@@ -10,6 +10,9 @@
 //                         scaled, SiLU'd and rounded to the operand type on the way (GroupNorm apply + SiLU + zero padding +
 //                         nearest x2 upsampling + im2col in ONE pass: 4 B read, taps * operand bytes written per element)
 //   reed_softmax_rows     softmax(scale * S) of the attention's fp32 score rows -> operand type
+// and the two passes of the encoder that the decoder has no counterpart of:
+//   reed_vae_image_rows   conv_in's row operand straight from the dataset's uint8 pixels (raw / 127.5 - 1, the 3x3 window)
+//   reed_vae_moments      quant_conv (8 x 8, fp32) + the diagonal Gaussian's (mean, std) as the NCHW moments the trainer reads
 // Built in all three libraries (operand type = bf16 / half / float).
 #include "../../include/reed_hip.h"
 #include "common.hpp"
@@ -176,6 +179,63 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   for (int c = lane; c < cols; c += 64) pr[c] = f2bf(expf(sr[c] * scale - m) * inv);
 }
 
+// ---- encoder: conv_in's row operand from uint8 pixels ---------------------------------------------------------------------
+// One thread per (row, group of 4 columns): row r - row0 = output position (b, y, x) of [B, H, W], column k = tap * 3 + c holds
+// raw[b, c, y + tap / 3 - 1, x + tap % 3 - 1] / 127.5 - 1 (the reference's `x.to(float32) / 127.5 - 1`, an IEEE division), 0 outside
+// the image (diffusers pads conv_in's input after the scaling: the pad is 0 in [-1, 1], not pixel 0), 0 in columns 27 and above.
+__global__ __launch_bounds__(256) void vae_image_rows_kernel(const uint8_t* __restrict__ raw, int H, int W, long row0, long nrows,
+                                                             int kcols, bf16* __restrict__ out, long ldo) {
+  const int G = kcols >> 2;
+  const long total = nrows * G;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long rr = i / G;
+    const int g = (int)(i - rr * G);
+    const unsigned r = (unsigned)(row0 + rr), HW = (unsigned)H * W;
+    const unsigned b = r / HW, rem = r - b * HW, y = rem / W, x = rem - y * W;
+    const uint8_t* img = raw + (long)b * 3 * HW;
+    typedef typename RowVec<4>::type vec_t;
+    vec_t o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = 4 * g + e, tap = k / 3, c = k - tap * 3;
+      const int yy = (int)y + tap / 3 - 1, xx = (int)x + tap % 3 - 1;
+      float v = 0.f;
+      if (k < 27 && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+        v = (float)img[(long)c * HW + (long)yy * W + xx] / 127.5f - 1.f;
+      o[e] = f2bf(v);
+    }
+    *(vec_t*)(out + rr * ldo + 4 * g) = o;
+  }
+}
+
+// ---- encoder tail: quant_conv + DiagonalGaussianDistribution ------------------------------------------------------------------
+// One thread per position p of [B, h, w]: the 8 values x = y[p, 0:8] of conv_out's fp32 rows, z = qb + qw x in fp32 (fixed order),
+// mean = z[0:4], logvar = clamp(z[4:8], -30, 20), std = exp(logvar / 2); out f32 [B, 8, h, w] = cat[mean, std] (NCHW: the lanes of
+// a wave store consecutive positions of one channel).
+__global__ __launch_bounds__(256) void vae_moments_kernel(const float* __restrict__ y, long ldc, int hw, long total,
+                                                          const float* __restrict__ qw, const float* __restrict__ qb,
+                                                          float* __restrict__ out) {
+  __shared__ float w[72];
+  if (threadIdx.x < 64) w[threadIdx.x] = qw[threadIdx.x];
+  else if (threadIdx.x < 72) w[threadIdx.x] = qb[threadIdx.x - 64];
+  __syncthreads();
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= total) return;
+  const float* src = y + p * ldc;
+  const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 4);
+  const float x[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  const long b = p / hw, q = p - b * hw;
+  float* ob = out + b * 8 * hw + q;
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {
+    float z = w[64 + o];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z = fmaf(w[o * 8 + i], x[i], z);
+    if (o >= 4) z = expf(0.5f * fminf(fmaxf(z, -30.f), 20.f));
+    ob[(long)o * hw] = z;
+  }
+}
+
 constexpr long GN_ROWS_MIN = 64;   // rows per chunk at least; at most 256 chunks per image
 
 int gn_chunks(long hw, long* rows_per_chunk) {
@@ -254,6 +314,38 @@ extern "C" int reed_softmax_rows(const float* s, int64_t lds, void* p, int64_t l
                  (long)lds, (long)ldp);
   REED_KLAUNCH(softmax_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, s, (long)lds, (bf16*)p, (long)ldp, rows,
                cols, scale);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
+extern "C" int reed_vae_image_rows(const uint8_t* raw, int B, int H, int W, int64_t row0, int64_t nrows, int kcols, void* out,
+                                   int64_t ldo, void* stream) {
+  REED_CHECK_ARG(raw && out && B > 0 && H > 0 && W > 0 && nrows > 0, "reed_vae_image_rows: empty problem");
+  REED_CHECK_ARG(kcols >= 28 && kcols % 4 == 0 && ldo >= kcols && ldo % 4 == 0,
+                 "reed_vae_image_rows: kcols=%d must be a multiple of 4 of at least 28, ldo=%ld >= kcols a multiple of 4", kcols,
+                 (long)ldo);
+  const long total = (long)B * H * W;
+  REED_CHECK_ARG(total * 3 < (1l << 31), "reed_vae_image_rows: %ld pixels (32-bit position arithmetic): pass fewer images", total);
+  REED_CHECK_ARG(row0 >= 0 && row0 + nrows <= total, "reed_vae_image_rows: rows [%ld, %ld) outside the %ld positions", (long)row0,
+                 (long)(row0 + nrows), total);
+  REED_CHECK_ARG(((uintptr_t)out % (4 * sizeof(bf16))) == 0, "reed_vae_image_rows: out must be aligned to 4 operand elements");
+  long blocks = ((long)nrows * (kcols / 4) + 255) / 256;
+  if (blocks > (1 << 20)) blocks = 1 << 20;
+  REED_KLAUNCH(vae_image_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, raw, H, W, (long)row0, (long)nrows,
+               kcols, (bf16*)out, (long)ldo);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
+extern "C" int reed_vae_moments(const float* y, int64_t ldc, int B, int h, int w, const float* qw, const float* qb, float* out,
+                                void* stream) {
+  REED_CHECK_ARG(y && qw && qb && out && B > 0 && h > 0 && w > 0, "reed_vae_moments: empty problem");
+  REED_CHECK_ARG(ldc >= 8 && ldc % 4 == 0 && ((uintptr_t)y % 16) == 0, "reed_vae_moments: y must be 16-byte aligned, ldc=%ld >= 8 a "
+                 "multiple of 4", (long)ldc);
+  const long total = (long)B * h * w;
+  REED_CHECK_ARG(total < (1l << 31) / 8, "reed_vae_moments: %ld positions: pass fewer images", total);
+  REED_KLAUNCH(vae_moments_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, (long)ldc, h * w, total,
+               qw, qb, out);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }

@@ -11,6 +11,10 @@ optional when no on-the-fly encoder needs them.
 decode and 2-3 small-file opens per image per step. Packing writes the same items, bit for bit and in the same
 (sorted-filename) order, into one memory-mappable array per field; `PackedDataset[i]` returns exactly what
 `CustomDataset[i]` returns.
+
+`encode_image_folder` (`python -m reed_amd.dataset encode`) writes the vae-sd/ half of that format from an image folder: the
+reference's `dataset_tools.py encode` for a directory source (same file names, same dataset.json, same f32 [8, H/8, W/8] moments),
+with the SD-VAE encoder on this package's kernels (reed_amd/vae.py) instead of diffusers.
 """
 import json
 import os
@@ -173,15 +177,150 @@ class SyntheticLatents(Dataset):
         return (torch.zeros(0, dtype=torch.uint8), moments, label, torch.zeros(0)) + zs
 
 
-if __name__ == "__main__":   # python -m reed_amd.dataset pack <data_dir> <out_dir> [--text-embeds-dir D] [--features-dirs A B] [--no-images]
+# ---------------- dataset encode: image folder -> vae-sd moments ----------------
+def _is_image(fname):
+    import PIL.Image
+    PIL.Image.init()
+    return "." + fname.split(".")[-1].lower() in PIL.Image.EXTENSION
+
+
+def list_image_folder(source_dir, max_images=None):
+    """The images `dataset_tools.py encode` takes from a directory, in its order, with its labels (open_image_folder): every file
+    under `source_dir` with an image extension, sorted by path; labels from <source_dir>/dataset.json {"labels": [[relpath,
+    label], ...]}, or, when it has none, the index of the sorted top-level directory name when there is more than one.
+    Returns [(path, label or None), ...] for the first `max_images`."""
+    found = []
+    for root, _dirs, files in os.walk(source_dir):
+        found += [os.path.join(root, f) for f in files]
+    paths = sorted(f for f in found if _is_image(f))
+    rel = {f: os.path.relpath(f, source_dir).replace("\\", "/") for f in paths}
+    labels = {}
+    meta = os.path.join(source_dir, "dataset.json")
+    if os.path.isfile(meta):
+        with open(meta) as f:
+            data = json.load(f)["labels"]
+        if data is not None:
+            labels = {x[0]: x[1] for x in data}
+    if not labels:
+        top = {r: r.split("/")[0] if "/" in r else "" for r in rel.values()}
+        index = {name: i for i, name in enumerate(sorted(set(top.values())))}
+        if len(index) > 1:
+            labels = {r: index[name] for r, name in top.items()}
+    n = len(paths) if max_images is None else min(len(paths), max_images)
+    return [(f, labels.get(rel[f])) for f in paths[:n]]
+
+
+def moments_fname(idx):
+    s = f"{idx:08d}"
+    return f"{s[:5]}/img-mean-std-{s}.npy"
+
+
+def moments_metadata(items):
+    """dataset.json of the encoded folder: {"labels": [[moments file, label], ...]}, or null when any image has no label."""
+    labels = [[moments_fname(i), lab] if lab is not None else None for i, (_, lab) in enumerate(items)]
+    return {"labels": labels if all(x is not None for x in labels) else None}
+
+
+class _ImageFiles(Dataset):
+    def __init__(self, paths):
+        self.paths = paths
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        import PIL.Image
+        img = np.array(PIL.Image.open(self.paths[i]).convert("RGB"))
+        return torch.from_numpy(img).permute(2, 0, 1).contiguous(), self.paths[i]
+
+
+def _collate_one_size(items):
+    first = items[0]
+    for img, path in items:
+        if img.shape != first[0].shape:
+            raise ValueError(f"{path} is {img.shape[2]}x{img.shape[1]} pixels but {first[1]} is {first[0].shape[2]}x{first[0].shape[1]}: "
+                             "dataset encode needs images of one size (as `convert` writes them)")
+    return torch.stack([img for img, _ in items]), [path for _, path in items]
+
+
+def encode_image_folder(source_dir, dest_dir, vae_ckpt, precision="fp32", batch_size=8, max_images=None, num_workers=4,
+                        device="cuda", log_every=0):
+    """Write <dest_dir>/{00000/img-mean-std-00000000.npy, ...} (f32 [8, H/8, W/8] = cat[mean, std] of the SD-VAE posterior) and
+    <dest_dir>/dataset.json for the images of `source_dir` (list_image_folder).  The files do not depend on `batch_size`."""
+    if not os.path.isdir(source_dir):
+        raise ValueError(f"{source_dir}: not a directory (zip sources are not supported)")
+    if dest_dir.lower().endswith(".zip"):
+        raise ValueError(f"{dest_dir}: zip destinations are not supported")
+    if os.path.isdir(dest_dir) and os.listdir(dest_dir):
+        raise ValueError(f"{dest_dir}: the destination folder must be empty")
+    items = list_image_folder(source_dir, max_images)
+    if not items:
+        raise ValueError(f"{source_dir}: no images")
+    from .vae import load_sd_vae_encoder
+    vae = load_sd_vae_encoder(vae_ckpt, device=device)
+    os.makedirs(dest_dir, exist_ok=True)
+    loader = torch.utils.data.DataLoader(_ImageFiles([p for p, _ in items]), batch_size=batch_size, shuffle=False,
+                                         num_workers=num_workers, pin_memory=True, collate_fn=_collate_one_size)
+    idx, shape = 0, None
+    for raw, paths in loader:
+        if shape is None:
+            shape, first = raw.shape[1:], paths[0]
+        elif raw.shape[1:] != shape:
+            raise ValueError(f"{paths[0]} is {raw.shape[3]}x{raw.shape[2]} pixels but {first} is {shape[2]}x{shape[1]}: "
+                             "dataset encode needs images of one size (as `convert` writes them)")
+        moments = vae.encode(raw.to(device, non_blocking=True), precision=precision).cpu().numpy()
+        for m in moments:
+            fn = os.path.join(dest_dir, moments_fname(idx))
+            os.makedirs(os.path.dirname(fn), exist_ok=True)
+            np.save(fn, m)
+            idx += 1
+        if log_every and idx % log_every < len(paths):
+            print(f"[dataset encode] {idx}/{len(items)}", flush=True)
+    meta = moments_metadata(items)
+    with open(os.path.join(dest_dir, "dataset.json"), "w") as f:
+        f.write(json.dumps(meta))
+    return meta
+
+
+def main(argv=None):
     import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cmd", choices=["pack"])
-    ap.add_argument("data_dir")
-    ap.add_argument("out_dir")
-    ap.add_argument("--text-embeds-dir", default=None)
-    ap.add_argument("--features-dirs", nargs="*", default=None)
-    ap.add_argument("--no-images", action="store_true")
-    a = ap.parse_args()
-    m = pack_dataset(a.data_dir, a.out_dir, a.text_embeds_dir, a.features_dirs, with_images=not a.no_images, log_every=10000)
-    print(json.dumps(m))
+    ap = argparse.ArgumentParser(prog="python -m reed_amd.dataset")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    p = sub.add_parser("pack", help="pack <data_dir> into memory-mappable arrays (PackedDataset)")
+    p.add_argument("data_dir")
+    p.add_argument("out_dir")
+    p.add_argument("--text-embeds-dir", default=None)
+    p.add_argument("--features-dirs", nargs="*", default=None)
+    p.add_argument("--no-images", action="store_true")
+    e = sub.add_parser("encode", help="encode an image folder into SD-VAE moments (vae-sd/)",
+                       description="Encode the images of a folder (e.g. the images/ output of the reference's `convert`) into the "
+                                   "f32 [8, H/8, W/8] SD-VAE moments cat[mean, std] that `train --data-dir` reads, as the reference's "
+                                   "`dataset_tools.py encode` does: <dest_dir>/00000/img-mean-std-00000000.npy, ... and dataset.json. "
+                                   "Runs on the GPU. Directories only: zip sources and zip destinations are not supported. All "
+                                   "images must have the same size; the destination must be empty or absent.")
+    e.add_argument("source_images_dir")
+    e.add_argument("dest_dir")
+    e.add_argument("--vae-ckpt", required=True, help="sd-vae-ft-{mse,ema}: a diffusers directory, .safetensors or .bin")
+    e.add_argument("--precision", choices=["fp32", "fp16", "bf16"], default="fp32",
+                   help="GEMM operand type (fp32: exact products; fp16 carries the mantissa of the reference's TF32 convolutions)")
+    e.add_argument("--batch-size", type=int, default=8, help="images per encoder call (the files do not depend on it)")
+    e.add_argument("--max-images", type=int, default=None)
+    e.add_argument("--num-workers", type=int, default=4, help="PNG decode processes (at most 16)")
+    a = ap.parse_args(argv)
+    if a.cmd == "pack":
+        m = pack_dataset(a.data_dir, a.out_dir, a.text_embeds_dir, a.features_dirs, with_images=not a.no_images, log_every=10000)
+        print(json.dumps(m))
+        return
+    if a.batch_size < 1 or (a.max_images is not None and a.max_images < 1) or not 0 <= a.num_workers <= 16:
+        ap.error("--batch-size and --max-images must be at least 1, --num-workers in [0, 16]")
+    try:
+        meta = encode_image_folder(a.source_images_dir, a.dest_dir, a.vae_ckpt, precision=a.precision, batch_size=a.batch_size,
+                                   max_images=a.max_images, num_workers=a.num_workers, log_every=10000)
+    except ValueError as err:
+        raise SystemExit(f"dataset encode: {err}")
+    n = len(meta["labels"]) if meta["labels"] is not None else None
+    print(json.dumps({"dest": a.dest_dir, "labelled": n is not None}))
+
+
+if __name__ == "__main__":   # python -m reed_amd.dataset pack <data_dir> <out_dir> [--text-embeds-dir D] [--features-dirs A B] [--no-images]
+    main()                   # python -m reed_amd.dataset encode <source_images_dir> <dest_dir> --vae-ckpt PATH [...]

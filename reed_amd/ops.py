@@ -607,3 +607,21 @@ def softmax_rows(s, lds, p, ldp, rows, cols, scale):
 def conv3x3(a, w, bias, out, ldc, B, Hi, Wi, C, N, upsample=False, accumulate=False):
     """out f32 [B*Ho*Wo, ldc] (+)= conv3x3(a operand-type NHWC [B, Hi, Wi, C]; w [N, 9C]) + bias f32 (reed_conv3x3, 16-bit builds)."""
     _call("reed_conv3x3", _p(a), _p(w), _p(bias), _p(out), ldc, B, Hi, Wi, C, N, int(upsample), int(accumulate), _stream())
+
+
+# ---------------- SD-VAE encoder passes (csrc/conv.hip, csrc/gemm_f32.hip, csrc/vae.hip) ----------------
+def conv3x3_down(a, w, bias, out, ldc, B, Hi, Wi, C, N, accumulate=False):
+    """out f32 [B*(Hi//2)*(Wi//2), ldc] (+)= conv3x3 at stride 2 of a (operand-type NHWC [B, Hi, Wi, C]) zero-padded by one row at
+    the bottom and one column at the right (diffusers' Downsample2D(padding=0)); w [N, 9C] in (ky, kx, ci) order, bias f32."""
+    _call("reed_conv3x3_down", _p(a), _p(w), _p(bias), _p(out), ldc, B, Hi, Wi, C, N, int(accumulate), _stream())
+
+
+def vae_image_rows(raw_u8, out, B, H, W, row0, nrows, kcols, ldo):
+    """out (operand type) [nrows, ldo] = rows [row0, row0 + nrows) of conv_in's operand from raw u8 [B, 3, H, W]: columns
+    tap * 3 + c = raw / 127.5 - 1 over the 3x3 window (0 outside the image), columns [27, kcols) zero."""
+    _call("reed_vae_image_rows", _p(raw_u8), B, H, W, row0, nrows, kcols, _p(out), ldo, _stream())
+
+
+def vae_moments(y, ldc, B, h, w, qw, qb, out):
+    """out f32 [B, 8, h, w] = cat[mean, std] of quant_conv(y[:, :8]) (qw f32 [8, 8], qb f32 [8]), logvar clamped to [-30, 20]."""
+    _call("reed_vae_moments", _p(y), ldc, B, h, w, _p(qw), _p(qb), _p(out), _stream())

@@ -16,6 +16,16 @@ Two forms of the same network over one set of parameters.  `decode(z)` is the pr
 GroupNorm-apply + SiLU + padding + nearest-x2 + im2col in one pass, softmax rows: csrc/vae.hip; no torch / MIOpen operator, and it
 raises without the library).  `decode_torch(z)` is the module tree's plain torch forward, kept for the CPU-side cross-check of
 the two restatements and as the GPU tests' second witness; nothing in the product calls it.
+
+`SDVAEEncoder` is the other half, for `python -m reed_amd.dataset encode` (the reference's image/preprocessing/encoders.py:72-80:
+`cat[d.mean, d.std]` of `AutoencoderKL.encode(raw / 127.5 - 1).latent_dist`): conv_in, four down blocks of two ResNet blocks
+(128, 128-256, 256-512, 512-512) with a stride-2 downsampler (zero pad (0, 1, 0, 1)) after the first three, the same mid block,
+GroupNorm + SiLU + conv_out to 8 channels (double_z), quant_conv (1x1, 8 -> 8), logvar clamped to [-30, 20], std = exp(logvar / 2);
+`load_sd_vae_encoder` reads the same checkpoint files.  Parity: UNPINNED as for the decoder — tests/test_vae_encoder_cpu.py holds
+`encode_torch` to an fp64 numpy restatement that walks the checkpoint keys, and to the published key / parameter surface
+(34,163,592 + 72).  `encode(raw_u8)` is the product (HIP kernels only, `_HipEncode`), `encode_torch(x)` the witness.  Default
+operands fp32: the reference encodes in fp32 with PyTorch's default TF32 convolutions (10 mantissa bits), which `fp16` operands
+match at the 16-bit rate; `bf16` is the fastest and coarsest.
 """
 import os
 import types
@@ -115,6 +125,82 @@ class _Decoder(nn.Module):
         return self.conv_out(F.silu(self.conv_norm_out(x)))
 
 
+class _Downsample(nn.Module):
+    """diffusers' Downsample2D(use_conv=True, padding=0): zero-pad one row at the bottom and one column at the right, then the
+    3x3 convolution at stride 2 (Ho = floor(Hi / 2), odd sizes included)."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)
+
+    def forward(self, x):
+        return self.conv(F.pad(x, (0, 1, 0, 1)))
+
+
+class _Down(nn.Module):
+    def __init__(self, cin, cout, n, groups, downsample):
+        super().__init__()
+        self.resnets = nn.ModuleList([_Resnet(cin if i == 0 else cout, cout, groups) for i in range(n)])
+        self.downsamplers = nn.ModuleList([_Downsample(cout)]) if downsample else None
+
+    def forward(self, x):
+        for r in self.resnets:
+            x = r(x)
+        return x if self.downsamplers is None else self.downsamplers[0](x)
+
+
+class _Encoder(nn.Module):
+    def __init__(self, in_channels, latent_channels, block_out_channels, layers_per_block, norm_num_groups):
+        super().__init__()
+        self.conv_in = nn.Conv2d(in_channels, block_out_channels[0], 3, padding=1)
+        downs, prev = [], block_out_channels[0]
+        for i, c in enumerate(block_out_channels):
+            downs.append(_Down(prev, c, layers_per_block, norm_num_groups, downsample=i < len(block_out_channels) - 1))
+            prev = c
+        self.down_blocks = nn.ModuleList(downs)
+        self.mid_block = _Mid(prev, norm_num_groups)
+        self.conv_norm_out = nn.GroupNorm(norm_num_groups, prev, eps=1e-6)
+        self.conv_out = nn.Conv2d(prev, 2 * latent_channels, 3, padding=1)      # double_z: mean and logvar
+
+    def forward(self, x):
+        x = self.conv_in(x)
+        for d in self.down_blocks:
+            x = d(x)
+        x = self.mid_block(x)
+        return self.conv_out(F.silu(self.conv_norm_out(x)))
+
+
+class SDVAEEncoder(nn.Module):
+    """`encode(raw)` == cat[d.mean, d.std] of `d = AutoencoderKL.encode(raw / 127.5 - 1).latent_dist`, the moments the reference's
+    `dataset_tools.py encode` stores: raw u8 [B, 3, H, W] -> f32 [B, 8, H / 8, W / 8] (2 * latent_channels)."""
+
+    def __init__(self, latent_channels=4, in_channels=3, block_out_channels=(128, 256, 512, 512), layers_per_block=2,
+                 norm_num_groups=32, scaling_factor=0.18215):
+        super().__init__()
+        self.scaling_factor = scaling_factor
+        self.encoder = _Encoder(in_channels, latent_channels, tuple(block_out_channels), layers_per_block, norm_num_groups)
+        self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
+
+    @torch.no_grad()
+    def encode_torch(self, x):
+        """x [B, 3, H, W] in [-1, 1] -> cat[mean, std], the module tree on torch operators (tests only: the witness)."""
+        mean, logvar = self.quant_conv(self.encoder(x)).chunk(2, dim=1)
+        return torch.cat([mean, torch.exp(0.5 * logvar.clamp(-30.0, 20.0))], dim=1)
+
+    @torch.no_grad()
+    def encode(self, raw, precision="fp32"):
+        """raw u8 [B, 3, H, W] on the GPU -> moments f32 [B, 8, H / 8, W / 8], on the HIP kernels.  precision = the GEMM operand
+        type: "fp32" (default: exact fp32 products), "fp16" / "bf16" (the 16-bit MFMA convolutions; channel counts must then be
+        multiples of 128).  The reference encodes in fp32 with PyTorch's default TF32 convolutions, whose operands keep 10
+        mantissa bits: fp16 operands carry the same mantissa, so "fp16" is the closest cheap match, "fp32" an exact superset."""
+        ops.require_cuda(raw, "images")
+        if getattr(self, "_hip", None) is None:
+            self._hip = _HipEncode(self)
+        return self._hip.encode(raw, precision)
+
+    forward = encode
+
+
 class SDVAEDecoder(nn.Module):
     """`decode(z)` == `AutoencoderKL.decode(z).sample`: z [B, 4, h, w] (already divided by the 0.18215 latent scale, as the
     reference's call sites do) -> images [B, 3, 8h, 8w] in [-1, 1]."""
@@ -148,13 +234,13 @@ def _round_up(n, m):
     return (n + m - 1) // m * m
 
 
-class _HipDecode:
-    """`SDVAEDecoder.decode` on the library.  Activations: fp32 NHWC, i.e. the row-major matrix [B*H*W, C].  A convolution is
-    reed_conv_rows (its row operand: GroupNorm apply + SiLU + zero padding + nearest x2 + the 9 taps, one pass) followed by
-    reed_gemm NT with epilogue 6 (fp32 + bias; `accumulate` adds onto the residual in place); the rows are produced in chunks of
-    at most `WS_BYTES` so the operand never exceeds that, whatever the batch.  Weights are repacked once per precision to
-    [Cout, 9*Cin] in (ky, kx, ci) order, K / N zero-padded to the kernels' granules (K 64, N 128 for the 16-bit builds; 4 / 4
-    for fp32)."""
+class _HipVAE:
+    """The passes `SDVAEDecoder.decode` and `SDVAEEncoder.encode` share, on the library.  Activations: fp32 NHWC, i.e. the
+    row-major matrix [B*H*W, C].  A convolution is reed_conv_rows (its row operand: GroupNorm apply + SiLU + zero padding + nearest
+    x2 + the 9 taps, one pass) followed by reed_gemm NT with epilogue 6 (fp32 + bias; `accumulate` adds onto the residual in place);
+    the rows are produced in chunks of at most `WS_BYTES` so the operand never exceeds that, whatever the batch.  Weights are
+    repacked once per precision to [Cout, 9*Cin] in (ky, kx, ci) order, K / N zero-padded to the kernels' granules (K 64, N 128
+    for the 16-bit builds; 4 / 4 for fp32)."""
     WS_BYTES = 1 << 30
 
     def __init__(self, vae):
@@ -202,13 +288,14 @@ class _HipDecode:
                                          table=tb)
         return tb
 
-    def _conv(self, x, name, mod, prec, taps, norm=None, silu=False, up=False, out=None, accumulate=False):
-        """x f32 [B, Hi, Wi, C] -> f32 [B, Ho, Wo, Cout_padded] (+= when accumulate) = conv(act(norm(upsample(x))))"""
+    def _conv(self, x, name, mod, prec, taps, norm=None, silu=False, up=False, out=None, accumulate=False, down=False):
+        """x f32 [B, Hi, Wi, C] -> f32 [B, Ho, Wo, Cout_padded] (+= when accumulate) = conv(act(norm(upsample(x)))); `down`: the
+        stride-2 convolution of x zero-padded by one row / column at the bottom / right (the encoder's downsamplers)"""
         B, Hi, Wi, C = x.shape
         wm, bm, co, k = self._pack(name, mod, prec)
         assert k == taps * C, (name, k, taps, C)
         npad, kcols = wm.shape
-        Ho, Wo = (Hi * 2, Wi * 2) if up else (Hi, Wi)
+        Ho, Wo = (Hi * 2, Wi * 2) if up else (Hi // 2, Wi // 2) if down else (Hi, Wi)
         M = B * Ho * Wo
         if out is None:
             out = torch.empty(B, Ho, Wo, npad, dtype=torch.float32, device=x.device)
@@ -224,9 +311,16 @@ class _HipDecode:
             for b0 in range(0, B, bc):
                 nb = min(bc, B - b0)
                 ops.conv_rows(x, act, B, Hi, Wi, C, 1, b0 * Hi * Wi, nb * Hi * Wi, C, C, table=tb, silu=silu)
-                ops.conv3x3(act, wm, self.bias32[(name, prec)], out.data_ptr() + b0 * Ho * Wo * npad * 4, npad, nb, Hi, Wi, C, npad,
-                            upsample=up, accumulate=accumulate)
+                if down:
+                    ops.conv3x3_down(act, wm, self.bias32[(name, prec)], out.data_ptr() + b0 * Ho * Wo * npad * 4, npad, nb, Hi, Wi,
+                                     C, npad, accumulate=accumulate)
+                else:
+                    ops.conv3x3(act, wm, self.bias32[(name, prec)], out.data_ptr() + b0 * Ho * Wo * npad * 4, npad, nb, Hi, Wi, C,
+                                npad, upsample=up, accumulate=accumulate)
             return out
+        if down:
+            raise ValueError(f"{name}: the stride-2 convolution needs {C} input channels to be a multiple of "
+                             f"{4 if prec == 'fp32' else 64} with precision {prec!r}")
         direct = prec == "fp32" and taps == 1 and norm is None and not silu and not up and kcols == C
         chunk = M if direct else min(M, max(1024, (self.WS_BYTES // (kcols * es)) // 1024 * 1024))
         cols = None if direct else self._workspace(chunk * kcols * es, x.device)
@@ -282,6 +376,10 @@ class _HipDecode:
         ops.gemm(ops.NT, ops.EPI_F32, o, wo, B * T, C, C, x, C, C, C, bias=bo, accumulate=True)           # x += out(O)
         return x
 
+
+class _HipDecode(_HipVAE):
+    """`SDVAEDecoder.decode` on the library (the passes of `_HipVAE`)."""
+
     def decode(self, z, precision="fp32"):
         v, d = self.vae, self.vae.decoder
         prev = ops.use(precision)
@@ -309,16 +407,75 @@ class _HipDecode:
             ops.use(prev)
 
 
+class _HipEncode(_HipVAE):
+    """`SDVAEEncoder.encode` on the library: conv_in from the pixels (reed_vae_image_rows + reed_gemm), the down blocks (the
+    stride-2 convolutions: reed_conv3x3_down), the mid block and conv_out as in the decoder, then quant_conv and the Gaussian's
+    (mean, std) in one pass (reed_vae_moments).  With 16-bit operands every reed_gemm goes to the 128 x 128 kernel: the
+    dispatcher picks other tiles (other MFMA shapes, other rounding) by M, which would make the moments depend on the batch size."""
+
+    def _image_conv(self, raw, prec):
+        conv = self.vae.encoder.conv_in
+        B, _, H, W = raw.shape
+        wm, bm, co, k = self._pack("encoder.conv_in", conv, prec)
+        assert k == 27, k
+        npad, kcols = wm.shape
+        M, es = B * H * W, ops.half_dtype(prec).itemsize
+        out = torch.empty(B, H, W, npad, dtype=torch.float32, device=raw.device)
+        chunk = min(M, max(1024, (self.WS_BYTES // (kcols * es)) // 1024 * 1024))
+        cols = self._workspace(chunk * kcols * es, raw.device)
+        for r0 in range(0, M, chunk):
+            n = min(chunk, M - r0)
+            ops.vae_image_rows(raw, cols, B, H, W, r0, n, kcols, kcols)
+            ops.gemm(ops.NT, ops.EPI_F32, cols, wm, n, npad, kcols, out.data_ptr() + r0 * npad * 4, kcols, kcols, npad, bias=bm)
+        return out
+
+    def encode(self, raw, precision="fp32"):
+        v, e = self.vae, self.vae.encoder
+        if raw.dtype != torch.uint8 or raw.ndim != 4 or raw.shape[1] != 3 or e.conv_in.in_channels != 3:
+            raise ValueError(f"images must be uint8 [B, 3, H, W] (got {raw.dtype} {tuple(raw.shape)})")
+        if v.quant_conv.out_channels != 8:
+            raise ValueError("reed_vae_moments takes 8 moment channels (latent_channels = 4)")
+        raw = raw.contiguous()
+        B = raw.shape[0]
+        prev, tile = ops.use(precision), ops.gemm_forced_tile()
+        pin = precision != "fp32" and tile != 128
+        if pin:
+            ops.gemm_force_tile(128)
+        try:
+            x = self._image_conv(raw, precision)
+            if x.shape[-1] != e.conv_in.out_channels:
+                raise ValueError(f"precision {precision!r} needs channel counts that are multiples of 128")
+            for i, d in enumerate(e.down_blocks):
+                for j, r in enumerate(d.resnets):
+                    x = self._resnet(x, f"encoder.down_blocks.{i}.resnets.{j}", r, precision)
+                if d.downsamplers is not None:
+                    x = self._conv(x, f"encoder.down_blocks.{i}.downsamplers.0.conv", d.downsamplers[0].conv, precision, 9,
+                                   down=True)
+            m = e.mid_block
+            x = self._resnet(x, "encoder.mid_block.resnets.0", m.resnets[0], precision)
+            x = self._attention(x, "encoder.mid_block.attentions.0", m.attentions[0], precision)
+            x = self._resnet(x, "encoder.mid_block.resnets.1", m.resnets[1], precision)
+            y = self._conv(x, "encoder.conv_out", e.conv_out, precision, 9, norm=e.conv_norm_out, silu=True)
+            _, h, w, ldc = y.shape
+            q = v.quant_conv
+            out = torch.empty(B, 8, h, w, dtype=torch.float32, device=raw.device)
+            ops.vae_moments(y, ldc, B, h, w, q.weight.detach().float().reshape(8, 8).contiguous(),
+                            q.bias.detach().float().contiguous(), out)
+            return out
+        finally:
+            if pin:
+                ops.gemm_force_tile(tile)
+            ops.use(prev)
+
+
 # attention parameters of the checkpoints published before diffusers renamed them (its loader converts these names too)
 _LEGACY_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
 
-def decoder_state_dict(sd):
-    """The decoder half of an AutoencoderKL state dict in this module's key names: drops encoder.* / quant_conv.*, maps the
-    legacy attention names, and squeezes 1x1-conv attention weights [C, C, 1, 1] of very old exports to Linear weights."""
+def _half_state_dict(sd, prefixes):
     out = {}
     for k, v in sd.items():
-        if not (k.startswith("decoder.") or k.startswith("post_quant_conv.")):
+        if not k.startswith(prefixes):
             continue
         parts = k.split(".")
         if "attentions" in parts:
@@ -333,7 +490,19 @@ def decoder_state_dict(sd):
     return out
 
 
-def load_sd_vae_decoder(path, device="cpu", dtype=torch.float32, **config):
+def decoder_state_dict(sd):
+    """The decoder half of an AutoencoderKL state dict in this module's key names: drops encoder.* / quant_conv.*, maps the
+    legacy attention names, and squeezes 1x1-conv attention weights [C, C, 1, 1] of very old exports to Linear weights."""
+    return _half_state_dict(sd, ("decoder.", "post_quant_conv."))
+
+
+def encoder_state_dict(sd):
+    """The encoder half (encoder.* and quant_conv.*) of an AutoencoderKL state dict, legacy attention names mapped as for the
+    decoder."""
+    return _half_state_dict(sd, ("encoder.", "quant_conv."))
+
+
+def _read_state_dict(path):
     """path: a diffusers model directory (diffusion_pytorch_model.safetensors or .bin inside), or such a file."""
     if os.path.isdir(path):
         for name in ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin"):
@@ -348,6 +517,19 @@ def load_sd_vae_decoder(path, device="cpu", dtype=torch.float32, **config):
     else:
         sd = torch.load(path, map_location="cpu", weights_only=True)
         sd = sd.get("state_dict", sd)
+    return sd
+
+
+def load_sd_vae_decoder(path, device="cpu", dtype=torch.float32, **config):
+    """path: a diffusers model directory (diffusion_pytorch_model.safetensors or .bin inside), or such a file."""
     vae = SDVAEDecoder(**{**SD_VAE_CONFIG, **config})
-    vae.load_state_dict(decoder_state_dict(sd), strict=True)
+    vae.load_state_dict(decoder_state_dict(_read_state_dict(path)), strict=True)
+    return vae.to(device=device, dtype=dtype).eval()
+
+
+def load_sd_vae_encoder(path, device="cpu", dtype=torch.float32, **config):
+    """The encoder half of the same files as load_sd_vae_decoder (path: a diffusers directory, .safetensors or .bin)."""
+    cfg = {k: v for k, v in {**SD_VAE_CONFIG, **config}.items() if k != "out_channels"}
+    vae = SDVAEEncoder(**cfg)
+    vae.load_state_dict(encoder_state_dict(_read_state_dict(path)), strict=True)
     return vae.to(device=device, dtype=dtype).eval()
