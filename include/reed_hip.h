@@ -205,7 +205,8 @@ int reed_final_layer_bwd_rows(const float* dout, const float* x, const float* me
                               const void* shift, const void* scale, int64_t ldmod, const void* w,
                               void* hbuf, void* dlin, void* dh, int B, int T, int D, int C, int P,
                               void* stream);
-/* mean over tokens for the text projector (sit.py:292,301): out bf16 [B,D] = bf16(mean_t x f32 [B,T,D]) */
+/* mean over tokens for the text projector (sit.py:292,301): out bf16 [B,D] = bf16(mean_t x f32 [B,T,D]); backward: dx[b,t,:] +=
+ * float(dmean[b,:]) / T.  B, T, D > 0 and non-null pointers, anything else is refused without a launch. */
 int reed_token_mean_fwd(const float* x, void* out, int B, int T, int D, void* stream);
 int reed_token_mean_bwd(const void* dmean, float* dx, int B, int T, int D, void* stream);
 

@@ -794,11 +794,15 @@ extern "C" int reed_reduce_mod_parts(const float* const* parts, const int64_t* s
 }
 
 extern "C" int reed_token_mean_fwd(const float* x, void* out, int B, int T, int D, void* stream) {
+  REED_CHECK_ARG(x && out, "token_mean_fwd: null pointer");
+  REED_CHECK_ARG(B > 0 && T > 0 && D > 0, "token_mean_fwd: bad B=%d T=%d D=%d", B, T, D);
   REED_KLAUNCH(token_mean_fwd_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, (hipStream_t)stream, x, (bf16*)out, T, D);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }
 extern "C" int reed_token_mean_bwd(const void* dmean, float* dx, int B, int T, int D, void* stream) {
+  REED_CHECK_ARG(dmean && dx, "token_mean_bwd: null pointer");
+  REED_CHECK_ARG(B > 0 && T > 0 && D > 0, "token_mean_bwd: bad B=%d T=%d D=%d", B, T, D);
   REED_KLAUNCH(token_mean_bwd_kernel, dim3(cdiv(D, 256), B), dim3(256), 0, (hipStream_t)stream,
                      (const bf16*)dmean, dx, T, D);
   REED_LAUNCH_CHECK();
