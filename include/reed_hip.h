@@ -42,7 +42,11 @@ int reed_half_kind(void);
  *   per-head partial dot products with R for reed_attention_bwd_dp (NN; returns 1002 without launching where the shape's
  *   kernel has no such epilogue); 14 / 15 = 1 / 2 with C = the activation's DERIVATIVE at the pre-activation instead of the
  *   pre-activation itself (what the backward needs: nothing else read the saved pre-activation), 16 = C bf16 =
- *   bf16(bf16(acc) * R): the activation backward as one multiply by that saved derivative.  N%128==0 (NT/NN with a
+ *   bf16(bf16(acc) * R): the activation backward as one multiply by that saved derivative; 17 = SwiGLU (DINOv2 ViT-g's
+ *   feed-forward, inference only): C bf16 [M, N/2] (ldc >= N/2) = bf16(float(bf16(silu(x1))) * x2) with x1 | x2 =
+ *   bf16(acc + bias), which is never stored.  NT only, no split-K, and Q / bias are PACKED: with g = 8, packed row 2gk + j is
+ *   row gk + j of the [N, K] weight (x1) and packed row 2gk + g + j its row N/2 + gk + j (x2), j < g; output column gk + j
+ *   (reed_amd/ops.py: swiglu_pack).  The fp32-operand library refuses it (1001).  N%128==0 (NT/NN with a
  *   bf16-output epilogue also N%144==0: the 256x144 tile of csrc/gemm144.hip); K%64==0 (NT/NN);
  *   M%128==0 (TN).  split_k>1 only with epilogue 8, or 6 with slab_stride>0 (C then holds split_k slabs;
  *   dbias likewise holds split_k slabs of M floats AT THE SAME slab_stride — put slab 0 of dbias right behind slab 0

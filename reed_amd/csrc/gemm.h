@@ -30,8 +30,13 @@ enum {
   // backward's dGELU / dSiLU epilogue only — so that epilogue becomes one multiply per element (EPI_MUL):
   EPI_GELU_G = 14,    // C bf16 = bf16(gelu_tanh'(pre)) (optional), C2 bf16 = gelu_tanh(pre), pre = bf16(acc+bias)
   EPI_SILU_G = 15,    // same with SiLU
-  EPI_MUL = 16        // C bf16 = bf16(bf16(acc) * R bf16)
+  EPI_MUL = 16,       // C bf16 = bf16(bf16(acc) * R bf16)
+  // the SwiGLU feed-forward of DINOv2 ViT-g (SwiGLUFFNFused: w3(silu(x1) * x2), x1 | x2 = w12(x)), inference only:
+  EPI_SWIGLU = 17     // C bf16 [M, N / 2] = bf16(bf16(silu(x1)) * x2), x12 = bf16(acc+bias) never stored.  NT only, on a weight (and
+                      //   bias) whose rows are interleaved in groups of SWIGLU_GROUP: packed rows 2 g k .. 2 g k + g - 1 are the x1 rows
+                      //   g k .. g k + g - 1, the next g their x2 partners (ops.swiglu_pack); output column g k + j
 };
+constexpr int SWIGLU_GROUP = 8;   // = the 8 columns a lane of tile_epilogue owns: the partner sits in the neighbouring lane
 
 struct GemmArgs {
   const bf16* P;

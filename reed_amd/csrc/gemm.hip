@@ -226,6 +226,9 @@ int dispatch_epi(int epi, const GemmArgs& a, int splits, hipStream_t s) {
     case EPI_LS_RES:
       if constexpr (LAY == LAY_NT) return launch<LAY, EPI_LS_RES>(a, splits, s);
       break;
+    case EPI_SWIGLU:
+      if constexpr (LAY == LAY_NT) return launch<LAY, EPI_SWIGLU>(a, splits, s);
+      break;
   }
   reed_set_error("reed_gemm: unknown epilogue %d", epi);
   return REED_ERR_ARG;
@@ -295,7 +298,7 @@ int reed_gemm_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t st
   {
     const bool epi_rows_free = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_QGELU || epi == EPI_GELU_ERF ||
                                epi == EPI_RES_BF16 || epi == EPI_LS_RES || epi == EPI_DGELU || epi == EPI_DSILU ||
-                               epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_MUL;
+                               epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_MUL || epi == EPI_SWIGLU;
     const int r = a.M % 256, mfull = a.M - r;
     if (g_force_tile == 0 && want != EPI_BF16_DOT && epi_rows_free && splits <= 1 && (layout == LAY_NT || layout == LAY_NN) &&
         r > 0 && r <= 128 && mfull >= 2048) {

@@ -374,6 +374,9 @@ int dispatch256(int epi, const GemmArgs& a, int splits, hipStream_t s) {
       case EPI_LS_RES:
         if constexpr (LAY == LAY_NT) return launch256<LAY, EPI_LS_RES>(a, splits, s);
         break;
+      case EPI_SWIGLU:
+        if constexpr (LAY == LAY_NT) return launch256<LAY, EPI_SWIGLU>(a, splits, s);
+        break;
     }
   }
   reed_set_error("reed_gemm(256^2): epilogue %d is not built for layout %d", epi, LAY);
@@ -426,7 +429,7 @@ bool reed_gemm256_preferred(int layout, int epi, const GemmArgs& a, int splits) 
   const bool ragged = (a.N % BN2) != 0 && (a.N % BN2) <= 128 &&
                       (epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_GATE_RES || epi == EPI_DGELU ||
                        epi == EPI_DSILU || epi == EPI_QGELU || epi == EPI_GELU_ERF || epi == EPI_RES_BF16 || epi == EPI_LS_RES ||
-                       epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_MUL);
+                       epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_MUL || epi == EPI_SWIGLU);
   double rounds256;
   if (ragged) {
     const double w = (double)tm * (tn - 1) + 0.6 * tm;

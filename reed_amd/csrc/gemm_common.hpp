@@ -86,6 +86,7 @@ struct EpiOps {
                                   EPI == EPI_GELU_G || EPI == EPI_SILU_G || EPI == EPI_MUL ||
                                   EPI == EPI_QGELU || EPI == EPI_GELU_ERF || EPI == EPI_RES_BF16) ? 1 + NI * 4
                                : EPI == EPI_BF16_DOT ? 1 + NI * 4
+                               : EPI == EPI_SWIGLU ? 1 + NI       // one half-width store per row group: a lane pair shares two rows
                                : EPI == EPI_GATE_RES ? 1 + NI * 12
                                : EPI == EPI_LS_RES ? 3 + NI * 8
                                                      : -1;  // fp32-accumulate epilogues: pointer path, not counted
@@ -336,6 +337,41 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& a, const f32x4 (&a
           st_bf16x8<SA | EPI_SAVED_AUX>(pre, rsC, oc + h * s8);    // empty descriptor when the pre-activation is not wanted
           st_bf16x8<SA>(act, rsC2, oc2 + h * t8);
         }
+      }
+    } else if constexpr (EPI == EPI_SWIGLU) {
+      // SwiGLU on the packed weight (gemm.h: groups of SWIGLU_GROUP = 8 columns): the even lane of a pair holds x1, the odd lane x2
+      // of the same 8 output columns, both for rows rt and rt + 8.  The pair swaps one row each (the rounded x12, four DPP moves): the
+      // even lane then owns row rt, the odd lane row rt + 8 of those columns — one 16-byte store per lane and row group, a wave-level
+      // store covers 64 contiguous bytes of 16 rows.  Roundings as eager bf16 autocast: x12, silu(x1), the product.
+      static_assert(SWIGLU_GROUP == 8, "the pairing below is the lane's 8-column chunk");
+      const long hn = a.N >> 1;                                   // columns of C
+      const __amdgpu_buffer_rsrc_t rsC =
+          epi_rsrc(a.C ? (const char*)a.C + (long)m0 * a.ldc * 2 : nullptr, ((rows - 1) * a.ldc + hn) * 2);
+      const bool odd = (lane & 1) != 0;
+      int oc = cv ? (int)(((rt + (odd ? 8 : 0)) * a.ldc + (nbase >> 1) + 8 * (rd_c >> 1)) * 2) : EPI_OOB;
+      const int s16 = (int)(16 * a.ldc * 2);
+#pragma unroll
+      for (int i = 0; i < NI; ++i, oc += s16) {
+        float v[2][8];
+        transpose(i, v);
+        bf16x8 keep, give;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          keep[e] = f2bf(odd ? v[1][e] : v[0][e]);
+          give[e] = f2bf(odd ? v[0][e] : v[1][e]);
+        }
+        const u32x4 gq = __builtin_bit_cast(u32x4, give);
+        u32x4 rq;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rq[k] = (unsigned)__builtin_amdgcn_update_dpp(0, (int)gq[k], 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+        const bf16x8 recv = __builtin_bit_cast(bf16x8, rq);
+        bf16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float x1 = bf2f(odd ? recv[e] : keep[e]), x2 = bf2f(odd ? keep[e] : recv[e]);
+          o[e] = f2bf(bfround(silu_f(x1)) * x2);
+        }
+        st_bf16x8<SA>(o, rsC, oc);
       }
     } else if constexpr (EPI == EPI_GATE_RES) {
       // y = bf16(acc+bias); x_out = x_in + float(bf16(gate*y))   (sit.py:134-135 under bf16 autocast)

@@ -122,7 +122,7 @@ int launch_skinny(const GemmArgs& a, hipStream_t stream) {
 bool reed_gemm_skinny_eligible(int layout, int epi, const GemmArgs& a, int splits) {
   const bool epi_ok = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_QGELU || epi == EPI_GELU_ERF ||
                       epi == EPI_GELU_G || epi == EPI_SILU_G ||
-                      epi == EPI_RES_BF16 || epi == EPI_LS_RES || epi == EPI_GATE_RES;
+                      epi == EPI_RES_BF16 || epi == EPI_LS_RES || epi == EPI_GATE_RES || epi == EPI_SWIGLU;
   return layout == LAY_NT && epi_ok && splits <= 1 && a.K % SK == 0 && a.K >= SK && a.N % 64 == 0 && a.M >= 1 &&
          (long)cdiv(a.M, 16) * (a.N / 64) < (1l << 30);
 }
@@ -139,6 +139,7 @@ int reed_gemm_skinny_launch(int epi, GemmArgs a, hipStream_t stream) {
     case EPI_RES_BF16: return launch_skinny<EPI_RES_BF16>(a, stream);
     case EPI_LS_RES: return launch_skinny<EPI_LS_RES>(a, stream);
     case EPI_GATE_RES: return launch_skinny<EPI_GATE_RES>(a, stream);
+    case EPI_SWIGLU: return launch_skinny<EPI_SWIGLU>(a, stream);
   }
   reed_set_error("gemm_skinny: epilogue %d not built", epi);
   return REED_ERR_UNSUPPORTED;

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import ops
-from .ops import EPI_BF16, EPI_GATE_RES, EPI_GELU_ERF, EPI_LS_RES, EPI_QGELU, EPI_RES_BF16, NT
+from .ops import EPI_BF16, EPI_GATE_RES, EPI_GELU_ERF, EPI_LS_RES, EPI_QGELU, EPI_RES_BF16, EPI_SWIGLU, NT
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -187,7 +187,18 @@ VIT_TOWERS = {
                             registers=4),
     "dinov2reg-vit-l": dict(embed=1024, depth=24, heads=16, patch=14, image=224, cls=True, final_norm=True, layerscale=True,
                             registers=4),
+    # "dinov2-vit-g" / "dinov2reg-vit-g": dinov2_vitg14[_reg], loaded by the same line of utils.py:92-104: 40 blocks of width 1536
+    # whose feed-forward is SwiGLUFFNFused (w12: 1536 -> 2 x 4096, w3(silu(x1) * x2)) instead of fc1 -> GELU -> fc2
+    "dinov2-vit-g": dict(embed=1536, depth=40, heads=24, patch=14, image=224, cls=True, final_norm=True, layerscale=True,
+                         ffn="swiglu"),
+    "dinov2reg-vit-g": dict(embed=1536, depth=40, heads=24, patch=14, image=224, cls=True, final_norm=True, layerscale=True,
+                            registers=4, ffn="swiglu"),
 }
+
+
+def swiglu_hidden(embed):
+    """Hidden width of DINOv2's SwiGLUFFNFused for mlp_ratio 4: two thirds of 4 * embed, rounded up to a multiple of 8."""
+    return (int(int(4 * embed) * 2 / 3) + 7) // 8 * 8
 
 
 class VitEncoder(nn.Module):
@@ -204,11 +215,21 @@ class VitEncoder(nn.Module):
     reference tree) is the same tower plus LayerScale (blocks.{i}.ls1.gamma / ls2.gamma: x + gamma * branch(x), the fp32
     gamma times the bf16 branch output in fp32) and, in the *_reg models, 4 register tokens inserted behind the class token
     after the position embedding was added (register_tokens); forward_features(...)['x_norm_patchtokens'] (train.py:356) =
-    the final-normed tokens without class and register tokens, which is what forward() returns."""
+    the final-normed tokens without class and register tokens, which is what forward() returns.
+    ffn="swiglu" (DINOv2 ViT-g: the hub's SwiGLUFFNFused) replaces fc1 / fc2 by blocks.{i}.mlp.w12 [2 Hd, embed] and mlp.w3
+    [embed, Hd], Hd = swiglu_hidden(embed): x1, x2 = w12(x).chunk(2); w3(silu(x1) * x2).  The product is formed in the epilogue
+    of the w12 GEMM (EPI_SWIGLU on the weight packed by ops.swiglu_pack): the [M, 2 Hd] pre-activation never reaches memory."""
 
     def __init__(self, embed=1024, depth=24, heads=16, patch=16, image=256, cls=True, final_norm=True, layerscale=False,
-                 registers=0):
+                 registers=0, ffn="mlp"):
         super().__init__()
+        if ffn not in ("mlp", "swiglu"):
+            raise ValueError(f"VitEncoder: ffn={ffn!r}: 'mlp' or 'swiglu'")
+        self.ffn = ffn
+        self.ffn_hidden = swiglu_hidden(embed) if ffn == "swiglu" else 4 * embed
+        if ffn == "swiglu" and self.ffn_hidden % 64:
+            raise ValueError(f"VitEncoder: SwiGLU hidden width {self.ffn_hidden} (embed={embed}) is not a multiple of 64 "
+                             "(the GEMMs need N % 128 == 0 for w12 and K % 64 == 0 for w3)")
         hd = embed // heads
         if embed % 128 or hd not in (64, 80) or heads * hd != embed:
             raise ValueError(f"VitEncoder: embed={embed} / heads={heads}: need embed % 128 == 0 and head_dim 64 or 80")
@@ -239,7 +260,10 @@ class VitEncoder(nn.Module):
             b.attn = nn.Module()
             b.attn.qkv, b.attn.proj = nn.Linear(embed, 3 * embed), nn.Linear(embed, embed)
             b.mlp = nn.Module()
-            b.mlp.fc1, b.mlp.fc2 = nn.Linear(embed, 4 * embed), nn.Linear(4 * embed, embed)
+            if ffn == "swiglu":
+                b.mlp.w12, b.mlp.w3 = nn.Linear(embed, 2 * self.ffn_hidden), nn.Linear(self.ffn_hidden, embed)
+            else:
+                b.mlp.fc1, b.mlp.fc2 = nn.Linear(embed, 4 * embed), nn.Linear(4 * embed, embed)
             if self.layerscale:
                 b.ls1, b.ls2 = nn.Module(), nn.Module()
                 b.ls1.gamma, b.ls2.gamma = nn.Parameter(torch.ones(embed)), nn.Parameter(torch.ones(embed))
@@ -267,9 +291,16 @@ class VitEncoder(nn.Module):
             w[:, :3 * self.patch * self.patch] = self.patch_embed.proj.weight.detach().reshape(E, -1).to(torch.bfloat16)
             bf = lambda t: t.detach().to(torch.bfloat16).contiguous()  # noqa: E731
             f32 = lambda t: t.detach().float().contiguous()            # noqa: E731
+
+            def ffn(b):   # fc1 = the GEMM into the hidden buffer, fc2 = the one back to the residual stream
+                if self.ffn == "swiglu":
+                    w12, b12 = ops.swiglu_pack(bf(b.mlp.w12.weight), bf(b.mlp.w12.bias))
+                    return dict(fc1_w=w12, fc1_b=b12, fc2_w=bf(b.mlp.w3.weight), fc2_b=bf(b.mlp.w3.bias))
+                return dict(fc1_w=bf(b.mlp.fc1.weight), fc1_b=bf(b.mlp.fc1.bias),
+                            fc2_w=bf(b.mlp.fc2.weight), fc2_b=bf(b.mlp.fc2.bias))
+
             blocks = [dict(qkv_w=bf(b.attn.qkv.weight), qkv_b=bf(b.attn.qkv.bias), proj_w=bf(b.attn.proj.weight),
-                           proj_b=bf(b.attn.proj.bias), fc1_w=bf(b.mlp.fc1.weight), fc1_b=bf(b.mlp.fc1.bias),
-                           fc2_w=bf(b.mlp.fc2.weight), fc2_b=bf(b.mlp.fc2.bias),
+                           proj_b=bf(b.attn.proj.bias), **ffn(b),
                            n1=(f32(b.norm1.weight), f32(b.norm1.bias)), n2=(f32(b.norm2.weight), f32(b.norm2.bias)),
                            ls1=f32(b.ls1.gamma) if self.layerscale else None,
                            ls2=f32(b.ls2.gamma) if self.layerscale else None)
@@ -303,7 +334,8 @@ class VitEncoder(nn.Module):
         ops.gemm(NT, EPI_BF16, cols, w["conv"], Mp, E, self.kp, patches, self.kp, self.kp, E, bias=w["conv_b"])
         xa, xb = f32(M, E), f32(M, E)
         ops.vit_tokens(patches, w["cls"], w["pos"], xa, B, T, E, nprefix=self.nprefix)
-        h, qkv, o, u = bf(M, E), bf(M, 3 * E), bf(M, E), bf(M, 4 * E)
+        Hd = self.ffn_hidden
+        h, qkv, o, u = bf(M, E), bf(M, 3 * E), bf(M, E), bf(M, Hd)
         one = w["ones"]
         # x + bf16(branch) in fp32: the gate-residual epilogue with a gate of ones; with LayerScale x + gamma * bf16(branch)
         res = (lambda g: dict(gate=g)) if self.layerscale else (lambda g: dict(gate=one, ldgate=0, rows_per_gate=T))
@@ -314,8 +346,11 @@ class VitEncoder(nn.Module):
             ops.attention_fwd(qkv, o, None, B, T, H, self.hd)
             ops.gemm(NT, epi_res, o, blk["proj_w"], M, E, E, xb, E, E, E, R=xa, ldr=E, bias=blk["proj_b"], **res(blk["ls1"]))
             ops.ln_affine_f32(xb, blk["n2"][0], blk["n2"][1], h, False, M, E)
-            ops.gemm(NT, EPI_GELU_ERF, h, blk["fc1_w"], M, 4 * E, E, None, E, E, 4 * E, C2=u, ldc2=4 * E, bias=blk["fc1_b"])
-            ops.gemm(NT, epi_res, u, blk["fc2_w"], M, E, 4 * E, xa, 4 * E, 4 * E, E, R=xb, ldr=E, bias=blk["fc2_b"],
+            if self.ffn == "swiglu":   # u = silu(x1) * x2 out of the w12 GEMM's epilogue
+                ops.gemm(NT, EPI_SWIGLU, h, blk["fc1_w"], M, 2 * Hd, E, u, E, E, Hd, bias=blk["fc1_b"])
+            else:
+                ops.gemm(NT, EPI_GELU_ERF, h, blk["fc1_w"], M, 4 * E, E, None, E, E, 4 * E, C2=u, ldc2=4 * E, bias=blk["fc1_b"])
+            ops.gemm(NT, epi_res, u, blk["fc2_w"], M, E, Hd, xa, Hd, Hd, E, R=xb, ldr=E, bias=blk["fc2_b"],
                      **res(blk["ls2"]))
         if self.final_norm:
             ops.ln_affine_f32(xa, w["norm"][0], w["norm"][1], xb, True, M, E)
@@ -391,7 +426,7 @@ def load_vit_encoder(enc_type, ckpt_path, device, resolution=256):
     """`jepa-vit-h`, `mocov3-vit-{b,l}`, `mae-vit-l` of image/utils.py:73-82,133-160 from the checkpoint files the reference
     names (ckpts/ijepa_vith.pth: state_dict['encoder'] with a 'module.' prefix; ckpts/mocov3_vit{b,l}.pth: ['state_dict']
     with 'module.base_encoder.' (fix_mocov3_state_dict, utils.py:27-52); ckpts/mae_vitl.pth: ['model']) or a plain state
-    dict; `dinov2[reg]-vit-{s,b,l}` of utils.py:92-104 from the torch.hub checkpoint file (dinov2_vit{s,b,l}14[_reg4]_pretrain.pth,
+    dict; `dinov2[reg]-vit-{s,b,l,g}` of utils.py:92-104 from the torch.hub checkpoint file (dinov2_vit{s,b,l,g}14[_reg4]_pretrain.pth,
     a plain state dict).  A learned pos_embed of another grid (DINOv2: 37 x 37, MAE: 14 x 14) is resampled to the tower's
     as utils.py:99-101,140-146 do with timm's resample_abs_pos_embed (bicubic, antialias; a load-time torch call on the CPU).
     resolution 512 (DINOv2 only, as in the reference): the tower takes 448-pixel input, 32 x 32 patches (T = 1025 / 1029),

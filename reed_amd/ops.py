@@ -15,7 +15,11 @@ from . import _lib
 NT, NN, TN = 0, 1, 2
 TN_TALL, TN_WIDE = 3, 4   # TN on the 256x128 / 128x256 tile of csrc/gemm_tn.hip (weight gradients)
 (EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB, EPI_ATOMIC_F32, EPI_QGELU,
- EPI_RES_BF16, EPI_GELU_ERF, EPI_LS_RES, EPI_BF16_DOT, EPI_GELU_G, EPI_SILU_G, EPI_MUL) = range(17)
+ EPI_RES_BF16, EPI_GELU_ERF, EPI_LS_RES, EPI_BF16_DOT, EPI_GELU_G, EPI_SILU_G, EPI_MUL, EPI_SWIGLU) = range(18)
+# EPI_SWIGLU pairs x1 / x2 of a SwiGLU feed-forward inside the GEMM epilogue: the rows of w12 are interleaved in groups of
+# SWIGLU_GROUP (csrc/gemm.h: the 8 columns one lane of the epilogue owns).  swiglu_pack / swiglu_unpack are the only code
+# that knows the layout.
+SWIGLU_GROUP = 8
 
 
 def _p(t):
@@ -94,6 +98,36 @@ def gemm(layout, epi, P, Q, M, N, K, C, ldp, ldq, ldc, C2=None, ldc2=0, R=None, 
     if key is not None:
         e1.record()
         gemm_probe_log.append((key, e0, e1))
+
+
+def _swiglu_perm(hd, device=None):
+    """perm[packed row] = w12 row: packed rows 2 g k + j <- g k + j (x1) and 2 g k + g + j <- hd + g k + j (x2), j < g."""
+    g = SWIGLU_GROUP
+    if hd % g:
+        raise ValueError(f"swiglu_pack: hidden width {hd} is not a multiple of SWIGLU_GROUP = {g}")
+    k = torch.arange(hd // g, device=device).view(-1, 1, 1)
+    half = torch.arange(2, device=device).view(1, -1, 1)
+    j = torch.arange(g, device=device).view(1, 1, -1)
+    return (half * hd + g * k + j).reshape(-1)
+
+
+def swiglu_pack(w12, b12=None):
+    """w12 [2 Hd, K] (rows [0, Hd) = x1, [Hd, 2 Hd) = x2: SwiGLUFFNFused's chunk(2)) and its bias [2 Hd] -> the row order
+    reed_gemm's EPI_SWIGLU pairs in its epilogue; output column g k + j of that GEMM is silu(x1) * x2 of hidden unit g k + j."""
+    perm = _swiglu_perm(w12.shape[0] // 2, w12.device)
+    return w12[perm].contiguous(), (b12[perm].contiguous() if b12 is not None else None)
+
+
+def swiglu_unpack(pw, pb=None):
+    """Inverse of swiglu_pack."""
+    perm = _swiglu_perm(pw.shape[0] // 2, pw.device)
+    w = torch.empty_like(pw)
+    w[perm] = pw
+    b = None
+    if pb is not None:
+        b = torch.empty_like(pb)
+        b[perm] = pb
+    return w, b
 
 
 def linear_fwd(x, w, bias, out, epi=EPI_BF16, act_out=None, R=None, gate=None, ldgate=0,

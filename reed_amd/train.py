@@ -16,8 +16,8 @@ PNG grids instead of wandb images (§9-2); checkpoints and
 args.json are written regardless of --report-to (§9-11); gradients are clipped once and the pre-clip norm is
 logged (§9-5); unknown --text-embeds-dir names get their width from the first .npy (§9-9).
 Additive flags: --features-dirs (precomputed frozen-encoder features, §8f N2), --encoder-ckpts (frozen image encoders run
-on the GPU every step from user-supplied state dicts, reed_amd/encoders.py; at --resolution 512 the dinov2[reg]-vit-* towers
-only, at 448 pixels as the reference runs them), --synthetic N (random latents),
+on the GPU every step from user-supplied state dicts, reed_amd/encoders.py: clip-vit-L, dinov2[reg]-vit-{s,b,l,g}, jepa-vit-h,
+mae-vit-l, mocov3-vit-{b,l}; at --resolution 512 the dinov2[reg]-vit-* towers only, at 448 pixels as the reference runs them), --synthetic N (random latents),
 --log-every.
 """
 import argparse
@@ -102,7 +102,8 @@ def parse_args(input_args=None):
                         help="precomputed frozen-encoder features, one dir per --enc-type entry")
     parser.add_argument("--encoder-ckpts", type=str, nargs="*", default=None,
                         help="state dicts of the frozen image encoders, one per --enc-type entry: the encoder runs on the "
-                             "GPU every step as in the reference (CLIP, DINOv2, I-JEPA, MoCo-v3, MAE towers: reed_amd/encoders.py, SURVEY.md §8f N2; "
+                             "GPU every step as in the reference (CLIP, DINOv2 S/B/L/g with and without registers, I-JEPA, MoCo-v3, MAE towers: "
+                             "reed_amd/encoders.py, SURVEY.md §8f N2; "
                              "at --resolution 512 dinov2[reg]-vit-* only)")
     parser.add_argument("--packed-dir", type=str, default=None,
                         help="train from a directory written by `python -m reed_amd.dataset pack` (memory-mapped arrays of "

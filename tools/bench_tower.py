@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Throughput of a frozen ViT target encoder on the HIP path: images/s through preprocess_raw_image + tower
 and the tower alone as a fraction of the bf16 MFMA roofline.  usage (GPU box): python tools/bench_tower.py [enc-type] [batch]
-enc-type: dinov2-vit-l (default; the C2 configuration's encoder), dinov2reg-vit-l, dinov2-vit-b, jepa-vit-h, mae-vit-l, mocov3-vit-l"""
+enc-type: dinov2-vit-l (default; the C2 configuration's encoder), dinov2reg-vit-l, dinov2-vit-b, dinov2-vit-g, dinov2reg-vit-g (SwiGLU
+feed-forward: 3 E Hd MACs per token where the others take 8 E^2), jepa-vit-h, mae-vit-l, mocov3-vit-l"""
 import json
 import os
 import sys
@@ -30,7 +31,8 @@ with torch.no_grad():
             p.copy_((torch.rand(p.shape, generator=g) * 2 - 1) * 0.05)
 enc = enc.to(dev).eval()
 E, L, T = enc.embed, enc.depth, enc.tokens
-mac = L * (T * 12 * E * E + 2 * T * T * E) + enc.npatch * 3 * enc.patch ** 2 * E
+ffn_mac = 3 * E * enc.ffn_hidden if enc.ffn == "swiglu" else 8 * E * E   # w12 + w3 / fc1 + fc2, per token
+mac = L * (T * (4 * E * E + ffn_mac) + 2 * T * T * E) + enc.npatch * 3 * enc.patch ** 2 * E
 raw = torch.randint(0, 256, (B, 3, 256, 256), dtype=torch.uint8, device=dev)
 for _ in range(2):
     out = enc.encode_raw(raw)

@@ -789,6 +789,54 @@ def g_dinov2_512(ref_sit, ref_loss, ref_samplers):
     save("dinov2_512", **out)
 
 
+def g_dinov2_g(ref_sit, ref_loss, ref_samplers):
+    """DINOv2 ViT-g's block (utils.py:92-104 loads dinov2_vitg14[_reg] with the same line as its siblings): the feed-forward is
+    the hub's SwiGLUFFNFused, w3(silu(x1) * x2) with x1 | x2 = w12(x).  The same independent port as g_dinov2 (transformers'
+    Dinov2Model / Dinov2WithRegistersModel) built with use_swiglu_ffn=True: its mlp.weights_in / mlp.weights_out take the hub's
+    w12 / w3 tensors as they are.  Width 384 (hidden width 1024), fp32 and bf16-autocast patch tokens: `plain` and `reg4` at 56 / 28
+    pixels, `p448` at 448 pixels with 4 registers (the --resolution 512 path: the 37 x 37 table resampled to 32 x 32 as in
+    g_dinov2_512; tokens sub-sampled [:, ::8]).  The parameters come from tests/swiglu_ref.py, which the tests share."""
+    from transformers import Dinov2Config, Dinov2Model, Dinov2WithRegistersConfig, Dinov2WithRegistersModel
+    from tests import swiglu_ref
+    out = {}
+    E, H = 384, 6
+    for tag, depth, image, reg, B, step in (("plain", 2, 56, 0, 3, 1), ("reg4", 2, 28, 4, 2, 1), ("p448", 1, 448, 4, 1, 8)):
+        P = swiglu_ref.hub_params(E, depth, H, image, reg)
+        if image == 448:
+            pe = detfill.normal((1, 1 + 37 * 37, E), 63) * 0.5
+            g = pe[:, 1:].reshape(1, 37, 37, E).permute(0, 3, 1, 2)
+            g = torch.nn.functional.interpolate(g, size=(32, 32), mode="bicubic", antialias=True).permute(0, 2, 3, 1).reshape(1, 1024, E)
+            P["pos_embed"] = torch.cat([pe[:, :1], g], 1)
+        kw = dict(hidden_size=E, num_hidden_layers=depth, num_attention_heads=H, mlp_ratio=4, image_size=image, patch_size=14,
+                  layer_norm_eps=1e-6, qkv_bias=True, use_swiglu_ffn=True)
+        m = (Dinov2WithRegistersModel(Dinov2WithRegistersConfig(num_register_tokens=reg, **kw)) if reg
+             else Dinov2Model(Dinov2Config(**kw)))
+        sd = {"embeddings.cls_token": P["cls_token"], "embeddings.mask_token": torch.zeros(1, E),
+              "embeddings.position_embeddings": P["pos_embed"],
+              "embeddings.patch_embeddings.projection.weight": P["patch_embed.proj.weight"],
+              "embeddings.patch_embeddings.projection.bias": P["patch_embed.proj.bias"],
+              "layernorm.weight": P["norm.weight"], "layernorm.bias": P["norm.bias"]}
+        if reg:
+            sd["embeddings.register_tokens"] = P["register_tokens"]
+        for i in range(depth):
+            b, h = f"blocks.{i}.", f"encoder.layer.{i}."
+            for j, nm in enumerate(("query", "key", "value")):
+                sd[h + f"attention.attention.{nm}.weight"] = P[b + "attn.qkv.weight"][j * E:(j + 1) * E]
+                sd[h + f"attention.attention.{nm}.bias"] = P[b + "attn.qkv.bias"][j * E:(j + 1) * E]
+            for src, dst in (("norm1", "norm1"), ("norm2", "norm2"), ("attn.proj", "attention.output.dense"),
+                             ("mlp.w12", "mlp.weights_in"), ("mlp.w3", "mlp.weights_out")):
+                sd[h + dst + ".weight"], sd[h + dst + ".bias"] = P[b + src + ".weight"], P[b + src + ".bias"]
+            sd[h + "layer_scale1.lambda1"], sd[h + "layer_scale2.lambda1"] = P[b + "ls1.gamma"], P[b + "ls2.gamma"]
+        m.load_state_dict(sd, strict=True)
+        m.eval()
+        x = detfill.normal((B, 3, image, image), 64)
+        with torch.no_grad():
+            out[tag + ".fp32"] = m(pixel_values=x).last_hidden_state[:, 1 + reg::step].numpy()
+            with torch.autocast("cpu", dtype=torch.bfloat16):
+                out[tag + ".bf16"] = m(pixel_values=x).last_hidden_state[:, 1 + reg::step].float().numpy()
+    save("dinov2_g", **out)
+
+
 def make_tiny_dataset(root, n=6, text_dim=16):
     """Deterministic tiny dataset in the reference's on-disk format (image/dataset.py:18-85; written by
     preprocessing/dataset_tools.py): images/XXXXX/imgNNNNNNNN.png, vae-sd/XXXXX/img-mean-std-NNNNNNNN.npy,
@@ -869,7 +917,7 @@ def g_init(ref_sit, ref_loss, ref_samplers):
 
 ALL = {"init": g_init, "static": g_static, "tiny": g_tiny, "tiny512": g_tiny512, "loss_units": g_loss_units, "samplers": g_samplers, "optim_toy": g_sched,
        "s2_c1": g_s2, "b2_align": g_b2, "xl2_c2": g_xl, "xl2_c2_gnorms": g_xl_gnorms, "xl2_c4": g_xl_c4, "xl2_infer": g_xl_infer, "samplers_long": g_samplers_long, "samplers_long_xl": g_samplers_long_xl, "fp16": g_fp16, "clip": g_clip, "dataset": g_dataset, "towers": g_towers, "dinov2": g_dinov2,
-       "dinov2_512": g_dinov2_512}
+       "dinov2_512": g_dinov2_512, "dinov2_g": g_dinov2_g}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
