@@ -134,7 +134,7 @@ int reed_reduce_mod_parts(const float* const* parts, const int64_t* strides, con
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Attention (timm Attention under sit.py:114-118; softmax(q k^T / sqrt(hd)) v), head_dim 64 or 72.
+ * Attention (timm Attention under sit.py:114-118; softmax(q k^T / sqrt(hd)) v), head_dim 64 or 72 (forward only: also 80).
  * qkv bf16 [B, T, 3, H, hd] as produced by the qkv Linear; o bf16 [B, T, H*hd]; lse f32 [B,H,T].
  * ------------------------------------------------------------------------------------------- */
 int reed_attention_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, int hd,
@@ -324,6 +324,12 @@ int reed_vit_tokens(const void* patches, const float* cls, int nprefix, const fl
  * mean3 / std3 are HOST pointers to 3 floats.  Bicubic = F.interpolate(mode='bicubic', align_corners=False). */
 int reed_preprocess_image(const uint8_t* raw, float* out, int B, int R, int S, const float* mean3, const float* std3,
                           int order, void* stream);
+/* SwiGLU as a row pass (DINOv2 ViT-g's SwiGLUFFNFused where reed_gemm has no epilogue 17: the fp32-operand library): x12 (operand
+ * type) [M, ld] = x1 | x2, the output of the w12 GEMM on the UNPACKED weight; u (operand type) [M, ldu], u[m, j] = T(T(silu(x12[m, j]))
+ * * x12[m, Hd + j]) with T the library's operand type: the rounding order of epilogue 17.  Every library exports it; in the 16-bit
+ * ones reed_gemm(0) + this equals reed_gemm(17) bit for bit.  Hd % 8 == 0, ld >= 2 Hd, ldu >= Hd, ld and ldu multiples of 8, 16-byte
+ * aligned pointers, M > 0; anything else is refused without a launch. */
+int reed_swiglu_rows(const void* x12, int64_t ld, void* u, int64_t ldu, int M, int Hd, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SD-VAE decoder: `vae.decode(latents / 0.18215).sample` of image/generate.py:87,156 and

@@ -6,7 +6,7 @@
 // is the plain one: exact fp32 on the vector ALUs, one thread per query row (forward, dQ) or per key row (dK, dV), the
 // other side's rows staged through LDS 32 at a time and read as wave-wide broadcasts, online softmax in 8-key chunks,
 // backward recomputed from the saved log-sum-exp in two deterministic kernels (no atomics).  Any T (256 / 1024 tokens at
-// 256^2 / 512^2), head_dim 64 or 72.  Same entry points and layouts as csrc/attention.hip, which is not part of this build.
+// 256^2 / 512^2), head_dim 64 or 72 (the forward also 80: the frozen ViT-H tower).  Same entry points and layouts as csrc/attention.hip, which is not part of this build.
 #include "../../include/reed_hip.h"
 #include "common.hpp"
 
@@ -250,10 +250,12 @@ __global__ __launch_bounds__(256) void attn_f32_bwd_dkv_kernel(const float* __re
 
 extern "C" int reed_attention_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, int hd, void* stream) {
   REED_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
-  REED_CHECK_ARG(hd == 64 || hd == 72, "attention (fp32 build): head_dim %d unsupported (64 or 72)", hd);
+  REED_CHECK_ARG(hd == 64 || hd == 72 || hd == 80, "attention forward (fp32 build): head_dim %d unsupported (64, 72 or 80)", hd);
   REED_CHECK_ARG(B > 0 && T > 0 && H > 0, "attention: bad dims B=%d T=%d H=%d", B, T, H);
   const dim3 grid(B * H, (T + 255) / 256);
   if (hd == 64) REED_KLAUNCH(attn_f32_fwd_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)qkv, (float*)o, lse, T, H);
+  else if (hd == 80)   // the frozen I-JEPA ViT-H tower in fp32 (reed_amd/encoders.py): forward only, the backward keeps refusing it
+    REED_KLAUNCH(attn_f32_fwd_kernel<80>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)qkv, (float*)o, lse, T, H);
   else REED_KLAUNCH(attn_f32_fwd_kernel<72>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)qkv, (float*)o, lse, T, H);
   REED_LAUNCH_CHECK();
   return REED_OK;

@@ -202,6 +202,35 @@ __global__ __launch_bounds__(256) void preprocess_image_kernel(const uint8_t* __
   out[idx] = r;
 }
 
+// SwiGLU as a row pass (DINOv2 ViT-g's SwiGLUFFNFused in the fp32-operand build, whose GEMM has no epilogue 17): x12 [M, ld] holds
+// x1 | x2 = the w12 GEMM's output on the UNPACKED weight, u [M, ldu] = T(T(silu(x1)) * x2) with T the build's operand type — the
+// rounding order of reed_gemm's epilogue 17 (csrc/gemm_common.hpp).  One 16-byte chunk per thread and step: blockIdx.x walks the
+// chunks of a row, blockIdx.y strides over the rows.
+constexpr int SW_VE = 16 / (int)sizeof(bf16);   // elements per 16-byte chunk: 8 (16-bit builds) or 4 (fp32)
+typedef __attribute__((ext_vector_type(SW_VE))) bf16 sw_vec;
+
+__device__ __forceinline__ float swiglu_silu(float x) {
+#if defined(REED_FP32)
+  return x / (1.f + expf(-x));   // exact-fp32 build: libm exp and an IEEE division, as gelu_erf_f keeps erff here
+#else
+  return silu_f(x);              // the epilogue's own form: the result is rounded to 16 bits
+#endif
+}
+
+__global__ __launch_bounds__(256) void swiglu_rows_kernel(const bf16* __restrict__ x12, long ld, bf16* __restrict__ u, long ldu,
+                                                          int M, int Hd) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= Hd / SW_VE) return;
+  for (int m = blockIdx.y; m < M; m += gridDim.y) {
+    const bf16* xr = x12 + (long)m * ld + c * SW_VE;
+    const sw_vec a = *(const sw_vec*)xr, b = *(const sw_vec*)(xr + Hd);
+    sw_vec o;
+#pragma unroll
+    for (int e = 0; e < SW_VE; ++e) o[e] = f2bf(bfround(swiglu_silu(bf2f(a[e]))) * bf2f(b[e]));
+    *(sw_vec*)(u + (long)m * ldu + c * SW_VE) = o;
+  }
+}
+
 }  // namespace
 
 extern "C" int reed_clip_im2col(const float* img, void* out, int B, int S, int P, int Kp, void* stream) {
@@ -266,6 +295,21 @@ extern "C" int reed_preprocess_image(const uint8_t* raw, float* out, int B, int 
   const long n = (long)B * 3 * S * S;
   REED_KLAUNCH(preprocess_image_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, raw, out, B, R, S, mean3[0],
                mean3[1], mean3[2], std3[0], std3[1], std3[2], order);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
+extern "C" int reed_swiglu_rows(const void* x12, int64_t ld, void* u, int64_t ldu, int M, int Hd, void* stream) {
+  REED_CHECK_ARG(x12 && u, "swiglu_rows: null pointer");
+  REED_CHECK_ARG(M > 0 && Hd > 0, "swiglu_rows: empty problem M=%d Hd=%d", M, Hd);
+  REED_CHECK_ARG(Hd % 8 == 0, "swiglu_rows: Hd=%d must be a multiple of 8", Hd);
+  REED_CHECK_ARG(ld >= 2 * (int64_t)Hd && ldu >= Hd && ld % 8 == 0 && ldu % 8 == 0,
+                 "swiglu_rows: ld=%ld (>= 2 Hd) and ldu=%ld (>= Hd) must be multiples of 8", (long)ld, (long)ldu);
+  REED_CHECK_ARG(((uintptr_t)x12 % 16) == 0 && ((uintptr_t)u % 16) == 0, "swiglu_rows: x12 and u must be 16-byte aligned");
+  const int gx = cdiv(Hd / SW_VE, 256);
+  const int gy = M < 1024 / gx ? M : (1024 / gx > 0 ? 1024 / gx : 1);   // about four workgroups per CU; the kernel strides over the rows
+  REED_KLAUNCH(swiglu_rows_kernel, dim3(gx, gy), dim3(256), 0, (hipStream_t)stream, (const bf16*)x12, (long)ld, (bf16*)u,
+               (long)ldu, M, Hd);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }

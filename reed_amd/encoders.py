@@ -16,6 +16,15 @@ Every contraction is a `reed_gemm` launch (patch-embedding conv as im2col + GEMM
 residual epilogue; c_fc with the QuickGELU epilogue; c_proj with the residual epilogue), attention is
 `reed_attention_fwd` (head_dim 64, T = 257: one 256-key tile + a ragged 1-key tile, online softmax), the row passes are
 csrc/encoder.hip. No CPU path.
+
+Precision.  The reference runs its frozen encoders inside `accelerator.autocast()` (image/train.py:351-357), so they follow
+`--mixed-precision`: fp16 (its default and README recipe), bf16, or no autocast at all = plain fp32.  Both towers here take
+`precision="bf16" | "fp16" | "fp32"` (train.py: --encoder-precision) and run on that build of the library (ops.use): the operand
+copies and every activation buffer are `ops.half_dtype(precision)`, the rounding points are the reference's under the matching
+autocast — operand-type linears / conv / attention with fp32 accumulation, LayerNorm in fp32, the ViT towers' fp32 residual —
+and in the fp32 build every one of them is the identity.  There is no fp32 fallback for a non-finite fp16 result: where an
+activation passes 65504 the reference under fp16 autocast saturates in the same place (CLIP's residual stream is fp16 there too),
+and a tower that silently widened would no longer compute what the reference does.  The default stays "bf16".
 """
 import torch
 from torch import nn
@@ -50,6 +59,12 @@ def preprocess_raw_image(raw, enc_type):
     ops.preprocess_image(raw, out, B, R, S, mean, std, order)
     return out
 
+def _check_precision(who, precision):
+    if precision not in ("bf16", "fp16", "fp32"):
+        raise ValueError(f"{who}: precision={precision!r}: 'bf16', 'fp16' or 'fp32'")
+    return precision
+
+
 CLIP_CONFIGS = {   # openai/CLIP vision towers the reference can name (utils.py:127: f"ViT-{model_config}/14")
     "L": dict(width=1024, layers=24, heads=16, patch=14, image=224),
     "B": dict(width=768, layers=12, heads=12, patch=14, image=224),   # (openai ships B/16 and B/32; kept for shape tests)
@@ -57,8 +72,9 @@ CLIP_CONFIGS = {   # openai/CLIP vision towers the reference can name (utils.py:
 
 
 class ClipVisionEncoder(nn.Module):
-    def __init__(self, width=1024, layers=24, heads=16, patch=14, image=224):
+    def __init__(self, width=1024, layers=24, heads=16, patch=14, image=224, precision="bf16"):
         super().__init__()
+        self.precision = _check_precision("ClipVisionEncoder", precision)
         if width % 128 or (width // heads) != 64:
             raise ValueError("ClipVisionEncoder: width must be a multiple of 128 with head_dim 64 (CLIP ViT-B/L towers)")
         self.width, self.layers, self.heads, self.patch, self.image = width, layers, heads, patch, image
@@ -87,7 +103,8 @@ class ClipVisionEncoder(nn.Module):
         self.transformer = nn.Module()
         self.transformer.resblocks = nn.ModuleList(blocks)
         self.requires_grad_(False)
-        self._bf = None   # bf16 operand copies of the GEMM weights, built on first use / after load_state_dict
+        self._bf = None   # operand-type copies of the GEMM weights, built on first use / after load_state_dict / for another precision
+        self._bf_prec = None
 
     # ---- weights -------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd, strict=False):
@@ -101,11 +118,12 @@ class ClipVisionEncoder(nn.Module):
         return super()._apply(fn, recurse)
 
     def _operands(self):
-        if self._bf is None:
+        if self._bf is None or self._bf_prec != self.precision:
             dev = self.conv1.weight.device
-            w = torch.zeros(self.width, self.kp, dtype=torch.bfloat16, device=dev)
-            w[:, :3 * self.patch * self.patch] = self.conv1.weight.detach().reshape(self.width, -1).to(torch.bfloat16)
-            bf = lambda t: t.detach().to(torch.bfloat16).contiguous()  # noqa: E731
+            half = ops.half_dtype(_check_precision("ClipVisionEncoder", self.precision))
+            w = torch.zeros(self.width, self.kp, dtype=half, device=dev)
+            w[:, :3 * self.patch * self.patch] = self.conv1.weight.detach().reshape(self.width, -1).to(half)
+            bf = lambda t: t.detach().to(half).contiguous()  # noqa: E731
             f32 = lambda t: t.detach().float().contiguous()            # noqa: E731
             blocks = []
             for b in self.transformer.resblocks:
@@ -117,6 +135,7 @@ class ClipVisionEncoder(nn.Module):
                     ln1=(f32(b.ln_1.weight), f32(b.ln_1.bias)), ln2=(f32(b.ln_2.weight), f32(b.ln_2.bias))))
             self._bf = dict(conv=w, cls=f32(self.class_embedding), pos=f32(self.positional_embedding),
                             ln_pre=(f32(self.ln_pre.weight), f32(self.ln_pre.bias)), blocks=blocks)
+            self._bf_prec = self.precision
         return self._bf
 
     # ---- forward -------------------------------------------------------------------------------------------------
@@ -127,7 +146,16 @@ class ClipVisionEncoder(nn.Module):
 
     @torch.no_grad()
     def forward(self, x):
-        """x: normalised images f32 [B,3,image,image] on the GPU -> bf16 [B, tokens-1, width]."""
+        """x: normalised images f32 [B,3,image,image] on the GPU -> [B, tokens-1, width] in the tower's operand type (bf16 / fp16;
+        fp32 in the fp32 build), as the reference's CLIP tower returns its autocast dtype.  fp16 results are not checked for
+        overflow and not recomputed in fp32: the reference under fp16 autocast saturates in the same places."""
+        prev = ops.use(_check_precision("ClipVisionEncoder", self.precision))
+        try:
+            return self._forward(x)
+        finally:
+            ops.use(prev)
+
+    def _forward(self, x):
         ops.require_cuda(x, "images")
         W, H, T, P = self.width, self.heads, self.tokens, self.patch
         if x.shape[1] != 3 or x.shape[-1] != self.image or x.shape[-2] != self.image:
@@ -135,7 +163,8 @@ class ClipVisionEncoder(nn.Module):
         B = x.shape[0]
         dev = x.device
         w = self._operands()
-        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)  # noqa: E731
+        half = ops.half_dtype(self.precision)
+        bf = lambda *s: torch.empty(s, dtype=half, device=dev)  # noqa: E731
         x = x.contiguous().float()
         Mp, M = B * (T - 1), B * T
         cols = bf(Mp, self.kp)
@@ -218,11 +247,16 @@ class VitEncoder(nn.Module):
     the final-normed tokens without class and register tokens, which is what forward() returns.
     ffn="swiglu" (DINOv2 ViT-g: the hub's SwiGLUFFNFused) replaces fc1 / fc2 by blocks.{i}.mlp.w12 [2 Hd, embed] and mlp.w3
     [embed, Hd], Hd = swiglu_hidden(embed): x1, x2 = w12(x).chunk(2); w3(silu(x1) * x2).  The product is formed in the epilogue
-    of the w12 GEMM (EPI_SWIGLU on the weight packed by ops.swiglu_pack): the [M, 2 Hd] pre-activation never reaches memory."""
+    of the w12 GEMM (EPI_SWIGLU on the weight packed by ops.swiglu_pack): the [M, 2 Hd] pre-activation never reaches memory.
+    precision="fp16" / "fp32" (module docstring): the same calls on the IEEE-half / fp32-operand library, "bf16" and "fp16"
+    reading "the 16-bit type" wherever this text says bf16.  The fp32 library's GEMM has no SwiGLU epilogue: there the
+    feed-forward is the plain GEMM on the unpacked w12 into [M, 2 Hd] followed by the row pass ops.swiglu_rows (same roundings,
+    all the identity in fp32), and its attention forward takes head_dim 80 (csrc/attention_f32.hip)."""
 
     def __init__(self, embed=1024, depth=24, heads=16, patch=16, image=256, cls=True, final_norm=True, layerscale=False,
-                 registers=0, ffn="mlp"):
+                 registers=0, ffn="mlp", precision="bf16"):
         super().__init__()
+        self.precision = _check_precision("VitEncoder", precision)
         if ffn not in ("mlp", "swiglu"):
             raise ValueError(f"VitEncoder: ffn={ffn!r}: 'mlp' or 'swiglu'")
         self.ffn = ffn
@@ -272,6 +306,7 @@ class VitEncoder(nn.Module):
         self.norm = nn.LayerNorm(embed, eps=1e-6)
         self.requires_grad_(False)
         self._bf = None
+        self._bf_prec = None
 
     def load_state_dict(self, sd, strict=False):
         sd = {k: v for k, v in sd.items() if not k.startswith(("head.", "fc_norm.")) and k != "mask_token"}
@@ -284,17 +319,21 @@ class VitEncoder(nn.Module):
         return super()._apply(fn, recurse)
 
     def _operands(self):
-        if self._bf is None:
+        if self._bf is None or self._bf_prec != self.precision:
             dev = self.pos_embed.device
             E = self.embed
-            w = torch.zeros(E, self.kp, dtype=torch.bfloat16, device=dev)
-            w[:, :3 * self.patch * self.patch] = self.patch_embed.proj.weight.detach().reshape(E, -1).to(torch.bfloat16)
-            bf = lambda t: t.detach().to(torch.bfloat16).contiguous()  # noqa: E731
+            half = ops.half_dtype(_check_precision("VitEncoder", self.precision))
+            w = torch.zeros(E, self.kp, dtype=half, device=dev)
+            w[:, :3 * self.patch * self.patch] = self.patch_embed.proj.weight.detach().reshape(E, -1).to(half)
+            bf = lambda t: t.detach().to(half).contiguous()  # noqa: E731
             f32 = lambda t: t.detach().float().contiguous()            # noqa: E731
 
             def ffn(b):   # fc1 = the GEMM into the hidden buffer, fc2 = the one back to the residual stream
                 if self.ffn == "swiglu":
-                    w12, b12 = ops.swiglu_pack(bf(b.mlp.w12.weight), bf(b.mlp.w12.bias))
+                    if self.precision == "fp32":   # no epilogue 17 in the fp32 build: the plain GEMM on w12 as it is, then swiglu_rows
+                        w12, b12 = bf(b.mlp.w12.weight), bf(b.mlp.w12.bias)
+                    else:
+                        w12, b12 = ops.swiglu_pack(bf(b.mlp.w12.weight), bf(b.mlp.w12.bias))
                     return dict(fc1_w=w12, fc1_b=b12, fc2_w=bf(b.mlp.w3.weight), fc2_b=bf(b.mlp.w3.bias))
                 return dict(fc1_w=bf(b.mlp.fc1.weight), fc1_b=bf(b.mlp.fc1.bias),
                             fc2_w=bf(b.mlp.fc2.weight), fc2_b=bf(b.mlp.fc2.bias))
@@ -311,12 +350,22 @@ class VitEncoder(nn.Module):
                 pos = torch.cat([pos[:1], torch.zeros(self.registers, E, device=dev), pos[1:]], 0).contiguous()
             self._bf = dict(conv=w, conv_b=bf(self.patch_embed.proj.bias), pos=pos, cls=cls,
                             norm=(f32(self.norm.weight), f32(self.norm.bias)), blocks=blocks,
-                            ones=torch.ones(E, dtype=torch.bfloat16, device=dev))
+                            ones=torch.ones(E, dtype=half, device=dev))
+            self._bf_prec = self.precision
         return self._bf
 
     @torch.no_grad()
     def forward(self, x):
-        """x: preprocessed images f32 [B,3,image,image] on the GPU -> f32 [B, patches, embed] (class token dropped)."""
+        """x: preprocessed images f32 [B,3,image,image] on the GPU -> f32 [B, patches, embed] (class token dropped), in every
+        precision: the residual stream and the final norm are fp32.  fp16 results are not checked for overflow and not recomputed
+        in fp32: the reference under fp16 autocast saturates in the same places."""
+        prev = ops.use(_check_precision("VitEncoder", self.precision))
+        try:
+            return self._forward(x)
+        finally:
+            ops.use(prev)
+
+    def _forward(self, x):
         ops.require_cuda(x, "images")
         E, H, T, P = self.embed, self.heads, self.tokens, self.patch
         if x.shape[1] != 3 or x.shape[-1] != self.image or x.shape[-2] != self.image:
@@ -324,7 +373,8 @@ class VitEncoder(nn.Module):
         B = x.shape[0]
         dev = x.device
         w = self._operands()
-        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)   # noqa: E731
+        half = ops.half_dtype(self.precision)
+        bf = lambda *s: torch.empty(s, dtype=half, device=dev)   # noqa: E731
         f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)    # noqa: E731
         x = x.contiguous().float()
         Mp, M = B * self.npatch, B * T
@@ -336,6 +386,8 @@ class VitEncoder(nn.Module):
         ops.vit_tokens(patches, w["cls"], w["pos"], xa, B, T, E, nprefix=self.nprefix)
         Hd = self.ffn_hidden
         h, qkv, o, u = bf(M, E), bf(M, 3 * E), bf(M, E), bf(M, Hd)
+        rows_swiglu = self.ffn == "swiglu" and self.precision == "fp32"
+        x12 = bf(M, 2 * Hd) if rows_swiglu else None
         one = w["ones"]
         # x + bf16(branch) in fp32: the gate-residual epilogue with a gate of ones; with LayerScale x + gamma * bf16(branch)
         res = (lambda g: dict(gate=g)) if self.layerscale else (lambda g: dict(gate=one, ldgate=0, rows_per_gate=T))
@@ -346,7 +398,10 @@ class VitEncoder(nn.Module):
             ops.attention_fwd(qkv, o, None, B, T, H, self.hd)
             ops.gemm(NT, epi_res, o, blk["proj_w"], M, E, E, xb, E, E, E, R=xa, ldr=E, bias=blk["proj_b"], **res(blk["ls1"]))
             ops.ln_affine_f32(xb, blk["n2"][0], blk["n2"][1], h, False, M, E)
-            if self.ffn == "swiglu":   # u = silu(x1) * x2 out of the w12 GEMM's epilogue
+            if rows_swiglu:            # fp32 build: x12 = w12(h) by the plain GEMM, u = silu(x1) * x2 by the row pass
+                ops.gemm(NT, EPI_BF16, h, blk["fc1_w"], M, 2 * Hd, E, x12, E, E, 2 * Hd, bias=blk["fc1_b"])
+                ops.swiglu_rows(x12, u, M, Hd)
+            elif self.ffn == "swiglu":   # u = silu(x1) * x2 out of the w12 GEMM's epilogue
                 ops.gemm(NT, EPI_SWIGLU, h, blk["fc1_w"], M, 2 * Hd, E, u, E, E, Hd, bias=blk["fc1_b"])
             else:
                 ops.gemm(NT, EPI_GELU_ERF, h, blk["fc1_w"], M, 4 * E, E, None, E, E, 4 * E, C2=u, ldc2=4 * E, bias=blk["fc1_b"])
@@ -422,7 +477,7 @@ def vit_resolution_error(enc_type, resolution):
     return RESOLUTION_256_ONLY.get(etype, f"no on-device tower for '{enc_type}' at --resolution {resolution}")
 
 
-def load_vit_encoder(enc_type, ckpt_path, device, resolution=256):
+def load_vit_encoder(enc_type, ckpt_path, device, resolution=256, precision="bf16"):
     """`jepa-vit-h`, `mocov3-vit-{b,l}`, `mae-vit-l` of image/utils.py:73-82,133-160 from the checkpoint files the reference
     names (ckpts/ijepa_vith.pth: state_dict['encoder'] with a 'module.' prefix; ckpts/mocov3_vit{b,l}.pth: ['state_dict']
     with 'module.base_encoder.' (fix_mocov3_state_dict, utils.py:27-52); ckpts/mae_vitl.pth: ['model']) or a plain state
@@ -430,14 +485,16 @@ def load_vit_encoder(enc_type, ckpt_path, device, resolution=256):
     a plain state dict).  A learned pos_embed of another grid (DINOv2: 37 x 37, MAE: 14 x 14) is resampled to the tower's
     as utils.py:99-101,140-146 do with timm's resample_abs_pos_embed (bicubic, antialias; a load-time torch call on the CPU).
     resolution 512 (DINOv2 only, as in the reference): the tower takes 448-pixel input, 32 x 32 patches (T = 1025 / 1029),
-    and the hub's 37 x 37 pos_embed is resampled to 32 x 32; any other family raises ValueError with the reference's failure."""
+    and the hub's 37 x 37 pos_embed is resampled to 32 x 32; any other family raises ValueError with the reference's failure.
+    precision: "bf16" (default), "fp16" or "fp32" — the library build the tower runs on (module docstring)."""
+    _check_precision("load_vit_encoder", precision)
     why = vit_resolution_error(enc_type, resolution)
     if why:
         raise ValueError(f"{enc_type} at resolution {resolution}: {why}")
     cfg = VIT_TOWERS[enc_type]
     if resolution != 256:
         cfg = dict(cfg, image=224 * (resolution // 256))
-    enc = VitEncoder(**cfg)
+    enc = VitEncoder(**cfg, precision=precision)
     sd = torch.load(ckpt_path, map_location="cpu")
     for key in ("encoder", "state_dict", "model"):
         if isinstance(sd, dict) and key in sd and isinstance(sd[key], dict):
@@ -467,11 +524,11 @@ def load_vit_encoder(enc_type, ckpt_path, device, resolution=256):
     return enc.to(device).eval()
 
 
-def load_clip_encoder(model_config, ckpt_path, device):
+def load_clip_encoder(model_config, ckpt_path, device, precision="bf16"):
     """`clip-vit-{L}` of image/utils.py:123-131 from a user-supplied state dict (`clip.load(...)[0].visual.state_dict()`
-    or the full CLIP state dict, whose `visual.` prefix is stripped)."""
+    or the full CLIP state dict, whose `visual.` prefix is stripped).  precision: as load_vit_encoder."""
     cfg = CLIP_CONFIGS[model_config]
-    enc = ClipVisionEncoder(**cfg)
+    enc = ClipVisionEncoder(**cfg, precision=precision)
     sd = torch.load(ckpt_path, map_location="cpu")
     sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd
     if any(k.startswith("visual.") for k in sd):

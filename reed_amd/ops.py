@@ -572,6 +572,13 @@ def vit_tokens(patches, cls, pos, out, B, T, D, nprefix=None):
     _call("reed_vit_tokens", _p(patches), _p(cls), int(nprefix), _p(pos), _p(out), B, T, D, _stream())
 
 
+def swiglu_rows(x12, u, M, Hd, ld=None, ldu=None):
+    """u (operand type) [M, ldu] = T(T(silu(x12[:, :Hd])) * x12[:, Hd:2 Hd]) of x12 (operand type) [M, ld]: SwiGLU behind a plain
+    EPI_BF16 GEMM on the unpacked w12, with the roundings of EPI_SWIGLU (the fp32 build's ViT-g feed-forward: its GEMM has no
+    epilogue 17)."""
+    _call("reed_swiglu_rows", _p(x12), 2 * Hd if ld is None else ld, _p(u), Hd if ldu is None else ldu, M, Hd, _stream())
+
+
 def preprocess_image(raw_u8, out, B, R, S, mean, std, order):
     """image/train.py:53-74 on the device: uint8 [B,3,R,R] -> f32 [B,3,S,S]; order 0 = /255, bicubic, normalise (clip);
     order 1 = /255, normalise, bicubic (dinov2 / jepa); S == R: no resampling (mocov3 / mae)."""

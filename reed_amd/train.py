@@ -17,8 +17,9 @@ args.json are written regardless of --report-to (§9-11); gradients are clipped 
 logged (§9-5); unknown --text-embeds-dir names get their width from the first .npy (§9-9).
 Additive flags: --features-dirs (precomputed frozen-encoder features, §8f N2), --encoder-ckpts (frozen image encoders run
 on the GPU every step from user-supplied state dicts, reed_amd/encoders.py: clip-vit-L, dinov2[reg]-vit-{s,b,l,g}, jepa-vit-h,
-mae-vit-l, mocov3-vit-{b,l}; at --resolution 512 the dinov2[reg]-vit-* towers only, at 448 pixels as the reference runs them), --synthetic N (random latents),
---log-every.
+mae-vit-l, mocov3-vit-{b,l}; at --resolution 512 the dinov2[reg]-vit-* towers only, at 448 pixels as the reference runs them),
+--encoder-precision {bf16,fp16,fp32,match} (the arithmetic of those towers; match = follow --mixed-precision as the reference's
+autocast does), --synthetic N (random latents), --log-every.
 """
 import argparse
 import copy
@@ -105,6 +106,11 @@ def parse_args(input_args=None):
                              "GPU every step as in the reference (CLIP, DINOv2 S/B/L/g with and without registers, I-JEPA, MoCo-v3, MAE towers: "
                              "reed_amd/encoders.py, SURVEY.md §8f N2; "
                              "at --resolution 512 dinov2[reg]-vit-* only)")
+    parser.add_argument("--encoder-precision", type=str, default="bf16", choices=["bf16", "fp16", "fp32", "match"],
+                        help="arithmetic of the --encoder-ckpts towers: bf16 / fp16 operands with fp32 accumulation, or plain fp32. "
+                             "'match' follows --mixed-precision (fp16 -> fp16, bf16 -> bf16, no -> fp32), which is what the reference "
+                             "does (its encoders run inside accelerator.autocast(), image/train.py:351-357): recommended for parity "
+                             "with the reference, whose default recipe gives fp16 targets. The default stays bf16")
     parser.add_argument("--packed-dir", type=str, default=None,
                         help="train from a directory written by `python -m reed_amd.dataset pack` (memory-mapped arrays of "
                              "the same items as --data-dir, SURVEY.md §8f N3)")
@@ -118,6 +124,7 @@ def parse_args(input_args=None):
                         help="local sd-vae-ft checkpoint (diffusers layout): turns on the reference's preview sampling at step 1 "
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
+    args.encoder_precision = resolve_encoder_precision(args.encoder_precision, args.mixed_precision)   # args.json holds the result
     if args.encoder_ckpts and args.resolution != 256:
         from .encoders import vit_resolution_error
         items = [] if args.enc_type in (None, "None") else args.enc_type.split(",")
@@ -128,6 +135,14 @@ def parse_args(input_args=None):
                          f"towers run at 448 pixels); {'; '.join(why)}. At --resolution {args.resolution} pass --features-dirs, "
                          f"--packed-dir with features, or --synthetic")
     return args
+
+
+def resolve_encoder_precision(encoder_precision, mixed_precision):
+    """--encoder-precision -> the library build of the frozen towers: 'match' = what accelerator.autocast() gives the reference's
+    encoders under --mixed-precision (fp16 / bf16 autocast, or none: fp32)."""
+    if encoder_precision == "match":
+        return {"no": "fp32", "fp16": "fp16", "bf16": "bf16"}[mixed_precision]
+    return encoder_precision
 
 
 def encoder_specs(enc_type):
@@ -233,9 +248,9 @@ def main(args):
             etype, _arch, cfg = item.split("-")
             key = f"{etype}-vit-{cfg.lower()[0]}"
             if etype == "clip":
-                encoders.append(load_clip_encoder(cfg[0].upper(), path, device))
+                encoders.append(load_clip_encoder(cfg[0].upper(), path, device, precision=args.encoder_precision))
             elif key in VIT_TOWERS:
-                encoders.append(load_vit_encoder(key, path, device, resolution=args.resolution))
+                encoders.append(load_vit_encoder(key, path, device, resolution=args.resolution, precision=args.encoder_precision))
             else:
                 raise NotImplementedError(f"on-device frozen encoder '{item}': built are clip-vit-*, {sorted(VIT_TOWERS)} (the "
                                           "towers image/utils.py:55-164 defines, configures or fetches; for others use "
@@ -266,6 +281,8 @@ def main(args):
                      time_schedule=args.time_schedule, cutoffs=args.cutoffs, latents_scale=0.18215, latents_bias=0.0)
     logger.info(f"SiT Parameters: {sum(p.numel() for p in model.parameters()):,}")
     logger.info(f"Encoders for Alignment {enc_names}; weights {args.repa_coeff}")
+    if encoders:
+        logger.info(f"frozen encoders: {', '.join(args.enc_type.split(','))} at {args.encoder_precision}")
 
     optimizer = FusedAdamWEMA(model, ema, lr=args.learning_rate, betas=(args.adam_beta1, args.adam_beta2),
                               weight_decay=args.adam_weight_decay, eps=args.adam_epsilon,
