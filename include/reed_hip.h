@@ -100,6 +100,7 @@ int reed_reduce_slabs(const float* slabs, int64_t stride, int nslabs, float* out
  *   h[m,:] = bf16( LN(x[m,:]) * bf16(1+scale[b,:]) + shift[b,:] ),  b = m / T
  * x f32 [M,D]; shift/scale bf16 with row stride ldmod; h bf16 [M,D]; mean/rstd f32 [M] (optional).
  * scale==NULL -> plain cast f32->bf16 of x (projector input cast, sit.py:292).
+ * mean and rstd are given together or both NULL; one without the other is refused without a launch.
  * ------------------------------------------------------------------------------------------- */
 int reed_ln_modulate_fwd(const float* x, const void* shift, const void* scale, int64_t ldmod,
                          void* h, float* mean, float* rstd, int M, int D, int T, float eps,
@@ -204,7 +205,9 @@ int reed_final_layer_fwd(const float* x, const void* shift, const void* scale, i
                          const void* w, const void* bias, float* out, float* mean, float* rstd,
                          int B, int T, int D, int C, int P, float eps, void* stream);
 /* backward, row part: recompute h = bf16(modulate(LN(x))) -> hbuf bf16 [M,D]; dlin bf16 [M, P*P*C] = patchify(dout);
- * dh bf16 [M,D] = dlin @ W.  Follow with reed_ln_modulate_bwd(dh, ...) and reed_smallk_wgrad(hbuf, dlin) */
+ * dh bf16 [M,D] = dlin @ W.  Follow with reed_ln_modulate_bwd(dh, ...) and reed_smallk_wgrad(hbuf, dlin).
+ * B, T > 0 and T a square (dout is [B,C,HW,HW] with HW = sqrt(T) * P), as in the forward: anything else is refused
+ * without a launch. */
 int reed_final_layer_bwd_rows(const float* dout, const float* x, const float* mean, const float* rstd,
                               const void* shift, const void* scale, int64_t ldmod, const void* w,
                               void* hbuf, void* dlin, void* dh, int B, int T, int D, int C, int P,
@@ -216,6 +219,7 @@ int reed_token_mean_bwd(const void* dmean, float* dx, int B, int T, int D, void*
 
 /* ---------------------------------------------------------------------------------------------
  * SILoss arithmetic (loss.py:49-64,153-237)
+ * Every entry point refuses B, per / half, T or Z <= 0 and null pointers without a launch.
  * ------------------------------------------------------------------------------------------- */
 /* sample_posterior (train.py:84-91): out [B,half] = (moments[:, :half] + moments[:, half:] * eps) * scale + bias */
 int reed_sample_posterior(const float* moments, const float* eps, float* out, int B, int64_t half,

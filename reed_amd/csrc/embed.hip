@@ -633,6 +633,9 @@ extern "C" int reed_final_layer_bwd_rows(const float* dout, const float* x, cons
                                          void* stream) {
   REED_CHECK_ARG(dout && x && mean && rstd && shift && scale && w && hbuf && dlin && dh, "final_layer_bwd_rows: null pointer");
   REED_CHECK_ARG(D % 4 == 0 && D <= 256 * MAXV, "final_layer: D=%d unsupported", D);
+  REED_CHECK_ARG(B > 0 && T > 0, "final_layer_bwd_rows: bad B=%d T=%d", B, T);
+  int G = (int)(sqrtf((float)T) + 0.5f);
+  REED_CHECK_ARG(G * G == T, "final_layer_bwd_rows: T=%d is not a square grid", T);   // HW = G * P: dout is read through it
   const int NO = P * P * C;
   const long wb = (long)NO * D * sizeof(bf16);
   if (wb + 4 * NO * (long)sizeof(float) <= 64 * 1024 && (NO * D) % 8 == 0 && ((uintptr_t)w % 16) == 0) {

@@ -119,6 +119,7 @@ extern "C" int reed_interpolant(const float* x, const float* noise, const float*
                                 int B, int64_t per, int path_type, void* stream) {
   REED_CHECK_ARG(x && noise && t && xt && target, "interpolant: null pointer");
   REED_CHECK_ARG(path_type == 0 || path_type == 1, "interpolant: path_type %d (0 linear, 1 cosine)", path_type);
+  REED_CHECK_ARG(B > 0 && per > 0, "interpolant: bad B=%d per=%ld", B, (long)per);
   REED_KLAUNCH(interpolant_kernel, dim3(cdiv(per, 1024), B), dim3(256), 0, (hipStream_t)stream, x, noise, t, xt,
                      target, (long)per, path_type);
   REED_LAUNCH_CHECK();
@@ -127,6 +128,7 @@ extern "C" int reed_interpolant(const float* x, const float* noise, const float*
 extern "C" int reed_sample_posterior(const float* moments, const float* eps, float* out, int B, int64_t half,
                                      float scale, float bias, void* stream) {
   REED_CHECK_ARG(moments && eps && out, "sample_posterior: null pointer");
+  REED_CHECK_ARG(B > 0 && half > 0, "sample_posterior: bad B=%d half=%ld", B, (long)half);
   REED_KLAUNCH(sample_posterior_kernel, dim3(cdiv(half, 1024), B), dim3(256), 0, (hipStream_t)stream, moments, eps,
                      out, (long)half, scale, bias);
   REED_LAUNCH_CHECK();
@@ -134,6 +136,7 @@ extern "C" int reed_sample_posterior(const float* moments, const float* eps, flo
 }
 extern "C" int reed_mse_fwd(const float* out, const float* target, float* loss, int B, int64_t per, void* stream) {
   REED_CHECK_ARG(out && target && loss, "mse_fwd: null pointer");
+  REED_CHECK_ARG(B > 0 && per > 0, "mse_fwd: bad B=%d per=%ld", B, (long)per);
   REED_KLAUNCH(mse_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, out, target, loss, (long)per);
   REED_LAUNCH_CHECK();
   return REED_OK;
@@ -141,6 +144,7 @@ extern "C" int reed_mse_fwd(const float* out, const float* target, float* loss, 
 extern "C" int reed_mse_bwd(const float* out, const float* target, const float* gscale, float* dout, int B,
                             int64_t per, void* stream) {
   REED_CHECK_ARG(out && target && gscale && dout, "mse_bwd: null pointer");
+  REED_CHECK_ARG(B > 0 && per > 0, "mse_bwd: bad B=%d per=%ld", B, (long)per);
   REED_KLAUNCH(mse_bwd_kernel, dim3(cdiv(per, 1024), B), dim3(256), 0, (hipStream_t)stream, out, target, gscale,
                      dout, (long)per);
   REED_LAUNCH_CHECK();
@@ -149,6 +153,7 @@ extern "C" int reed_mse_bwd(const float* out, const float* target, const float* 
 extern "C" int reed_cosine_fwd(const void* zt, const float* z, float* rowdot, float* loss, int B, int T, int Z,
                                void* stream) {
   REED_CHECK_ARG(zt && z && rowdot && loss, "cosine_fwd: null pointer");
+  REED_CHECK_ARG(B > 0 && T > 0 && Z > 0, "cosine_fwd: bad B=%d T=%d Z=%d", B, T, Z);
   REED_CHECK_ARG(Z % 4 == 0, "cosine: Z=%d must be a multiple of 4", Z);
   const int M = B * T;
   REED_KLAUNCH(cosine_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16*)zt, z,
@@ -160,6 +165,7 @@ extern "C" int reed_cosine_fwd(const void* zt, const float* z, float* rowdot, fl
 extern "C" int reed_cosine_bwd(const void* zt, const float* z, const float* gscale, void* dzt, int B, int T,
                                int Z, void* stream) {
   REED_CHECK_ARG(zt && z && gscale && dzt, "cosine_bwd: null pointer");
+  REED_CHECK_ARG(B > 0 && T > 0 && Z > 0, "cosine_bwd: bad B=%d T=%d Z=%d", B, T, Z);
   REED_CHECK_ARG(Z % 4 == 0, "cosine: Z=%d must be a multiple of 4", Z);
   const int M = B * T;
   REED_KLAUNCH(cosine_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16*)zt, z,

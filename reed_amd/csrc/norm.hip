@@ -672,6 +672,7 @@ extern "C" int reed_ln_modulate_fwd(const float* x, const void* shift, const voi
   REED_CHECK_ARG(D % 4 == 0 && D <= 256 * MAXV, "ln_modulate: D=%d unsupported (multiple of 4, <= %d)", D, 256 * MAXV);
   REED_CHECK_ARG(M > 0 && T > 0, "ln_modulate: bad M=%d T=%d", M, T);
   REED_CHECK_ARG((scale == nullptr) == (shift == nullptr), "ln_modulate: shift and scale must both be given or both NULL");
+  REED_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "ln_modulate_fwd: mean and rstd must both be given or both NULL");
   if ((long)M * D * 4 >= (256l << 20))
     REED_KLAUNCH(ln_mod_fwd_kernel<true>, dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, x, (const bf16*)shift,
                  (const bf16*)scale, (long)ldmod, (bf16*)h, mean, rstd, M, D, T, eps);
