@@ -386,6 +386,36 @@ int reed_vae_image_rows(const uint8_t* raw, int B, int H, int W, int64_t row0, i
  * [8], fp32), mean = z[0:4], std = exp(clamp(z[4:8], -30, 20) / 2); out f32 [B, 8, h, w] = cat[mean, std] (NCHW). */
 int reed_vae_moments(const float* y, int64_t ldc, int B, int h, int w, const float* qw, const float* qb, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * `python -m reed_amd.dataset convert`: Pillow's 8-bit resampler (ImagingResample behind Image.resize on uint8), the crop / resize
+ * of the reference's image/preprocessing/dataset_tools.py convert (make_transform), bit for bit (csrc/resample.hip).  A resize is
+ * a horizontal pass, then a vertical one, each u8 -> u8: out = clip_0_255((2^21 + sum_t in[first + t] * k[t]) >> 22) in int32.  The
+ * host planner (reed_amd/resample.py) builds the int32 coefficients k as Pillow does and trims each pass to the window that later
+ * passes read.
+ * ------------------------------------------------------------------------------------------- */
+/* One pass ("level") for a ragged batch: item j is one pass of one image, independent of the others.  Images are interleaved RGB
+ * (byte 3 x + c of a row); image offsets and row pitches are multiples of 16 bytes.  Nothing is allocated and the host is never
+ * waited for.
+ *   items        n_items x 16 int32 words (16-byte aligned):
+ *                [0:2]  int64 byte offset of the source image in `src`      [2:4]  int64 byte offset of the destination
+ *                [4] source row pitch  [5] destination row pitch (bytes)      [6] source samples along the filtered axis
+ *                [7] out0, [8] nout: the outputs [out0, out0 + nout) along the filtered axis are computed
+ *                [9] oth0, [10] noth: over [oth0, oth0 + noth) of the other axis (columns in pixels for a vertical pass, rows
+ *                     for a horizontal one); source and destination share the coordinates of that axis
+ *                [11] first int32 of the item's coefficients in `coefs`    [12] first (first, taps) pair of the item in `bounds`
+ *                [13] ksize: coefficients per output; output out0 + i uses bounds[[12] + i] = (first source sample, taps <= ksize)
+ *                     and coefs[[11] + i * ksize + t], t < taps; first + t is clamped into [0, [6])
+ *                [14] kind: 0 horizontal, 1 vertical (both into `dst`, interleaved, at the output's own coordinates: row y at
+ *                     [2:4] + y * [5]), 2 vertical into `out` as planar u8 [3, nout, noth]: plane c, row i, column j of the window at
+ *                     [2:4] + c * [15] + i * [5] + j (noth % 4 == 0, [2:4] % 4 == 0)        [15] plane stride in bytes (kind 2)
+ *   tile_prefix  int32 [n_items + 1]: tile_prefix[j + 1] - tile_prefix[j] = ceil(work items of item j / 256), work items =
+ *                kind 0: noth * (((out0 + nout + 3) >> 2) - (out0 >> 2)); kind 1: nout * (((3 (oth0 + noth) + 3) >> 2) - ((3 oth0) >> 2));
+ *                kind 2: nout * noth / 4.  total_tiles = tile_prefix[n_items] = the grid.
+ * Written: exactly the window of each item (no pitch padding, nothing outside it).  dst may be NULL when no item has kind 0 / 1,
+ * out when none has kind 2.  n_items <= 0, total_tiles <= 0, a null table or a misaligned pointer is refused without a launch. */
+int reed_resample_u8(const uint8_t* src, uint8_t* dst, uint8_t* out, const void* items, const int32_t* tile_prefix, int n_items,
+                     int total_tiles, const int32_t* coefs, const int32_t* bounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

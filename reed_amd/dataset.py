@@ -15,6 +15,11 @@ decode and 2-3 small-file opens per image per step. Packing writes the same item
 `encode_image_folder` (`python -m reed_amd.dataset encode`) writes the vae-sd/ half of that format from an image folder: the
 reference's `dataset_tools.py encode` for a directory source (same file names, same dataset.json, same f32 [8, H/8, W/8] moments),
 with the SD-VAE encoder on this package's kernels (reed_amd/vae.py) instead of diffusers.
+
+`convert_image_folder` (`python -m reed_amd.dataset convert`) writes the images/ half from raw images of any sizes: the reference's
+`dataset_tools.py convert` for a directory source and destination (same file order, labels, file names, uncompressed PNGs with the
+same bytes), with Pillow's crop / resize arithmetic on the GPU (reed_amd/resample.py, csrc/resample.hip) or through Pillow itself,
+and optionally the vae-sd/ half from the same device batches.
 """
 import json
 import os
@@ -221,6 +226,31 @@ def moments_metadata(items):
     return {"labels": labels if all(x is not None for x in labels) else None}
 
 
+def _write_moments(dest_dir, idx, moments):
+    """Save a batch of moments (f32 [B, 8, h, w], any device) as the files idx, idx + 1, ...; returns the next index."""
+    for m in moments.cpu().numpy():
+        fn = os.path.join(dest_dir, moments_fname(idx))
+        os.makedirs(os.path.dirname(fn), exist_ok=True)
+        np.save(fn, m)
+        idx += 1
+    return idx
+
+
+def _write_metadata(dest_dir, meta):
+    with open(os.path.join(dest_dir, "dataset.json"), "w") as f:
+        f.write(json.dumps(meta))
+    return meta
+
+
+def _check_folders(source_dir, dest_dir):
+    if not os.path.isdir(source_dir):
+        raise ValueError(f"{source_dir}: not a directory (zip sources are not supported)")
+    if dest_dir.lower().endswith(".zip"):
+        raise ValueError(f"{dest_dir}: zip destinations are not supported")
+    if os.path.isdir(dest_dir) and os.listdir(dest_dir):
+        raise ValueError(f"{dest_dir}: the destination folder must be empty")
+
+
 class _ImageFiles(Dataset):
     def __init__(self, paths):
         self.paths = paths
@@ -247,12 +277,7 @@ def encode_image_folder(source_dir, dest_dir, vae_ckpt, precision="fp32", batch_
                         device="cuda", log_every=0):
     """Write <dest_dir>/{00000/img-mean-std-00000000.npy, ...} (f32 [8, H/8, W/8] = cat[mean, std] of the SD-VAE posterior) and
     <dest_dir>/dataset.json for the images of `source_dir` (list_image_folder).  The files do not depend on `batch_size`."""
-    if not os.path.isdir(source_dir):
-        raise ValueError(f"{source_dir}: not a directory (zip sources are not supported)")
-    if dest_dir.lower().endswith(".zip"):
-        raise ValueError(f"{dest_dir}: zip destinations are not supported")
-    if os.path.isdir(dest_dir) and os.listdir(dest_dir):
-        raise ValueError(f"{dest_dir}: the destination folder must be empty")
+    _check_folders(source_dir, dest_dir)
     items = list_image_folder(source_dir, max_images)
     if not items:
         raise ValueError(f"{source_dir}: no images")
@@ -268,18 +293,118 @@ def encode_image_folder(source_dir, dest_dir, vae_ckpt, precision="fp32", batch_
         elif raw.shape[1:] != shape:
             raise ValueError(f"{paths[0]} is {raw.shape[3]}x{raw.shape[2]} pixels but {first} is {shape[2]}x{shape[1]}: "
                              "dataset encode needs images of one size (as `convert` writes them)")
-        moments = vae.encode(raw.to(device, non_blocking=True), precision=precision).cpu().numpy()
-        for m in moments:
-            fn = os.path.join(dest_dir, moments_fname(idx))
-            os.makedirs(os.path.dirname(fn), exist_ok=True)
-            np.save(fn, m)
-            idx += 1
+        idx = _write_moments(dest_dir, idx, vae.encode(raw.to(device, non_blocking=True), precision=precision))
         if log_every and idx % log_every < len(paths):
             print(f"[dataset encode] {idx}/{len(items)}", flush=True)
-    meta = moments_metadata(items)
-    with open(os.path.join(dest_dir, "dataset.json"), "w") as f:
-        f.write(json.dumps(meta))
-    return meta
+    return _write_metadata(dest_dir, moments_metadata(items))
+
+
+# ---------------- dataset convert: raw images -> images/ (and vae-sd/) ----------------
+def image_fname(idx):
+    s = f"{idx:08d}"
+    return f"{s[:5]}/img{s}.png"
+
+
+def image_metadata(items):
+    """dataset.json of the converted folder: {"labels": [[image file, label], ...]}, or null when any image has no label."""
+    labels = [[image_fname(i), lab] if lab is not None else None for i, (_, lab) in enumerate(items)]
+    return {"labels": labels if all(x is not None for x in labels) else None}
+
+
+def check_convert_args(source_dir, dest_dir, resolution, transform):
+    """The refusals of `dataset convert`, each with its reason (ValueError)."""
+    from .resample import TRANSFORMS
+    _check_folders(source_dir, dest_dir)
+    if transform == "center-crop-wide":
+        raise ValueError("--transform center-crop-wide is not supported: its output is not square, and the dataset format needs "
+                         "square images")
+    if transform not in TRANSFORMS:
+        raise ValueError(f"--transform {transform}: one of {', '.join(TRANSFORMS)}")
+    if not isinstance(resolution, int) or resolution < 8 or resolution & (resolution - 1):
+        raise ValueError(f"--resolution {resolution}: the dataset format needs square power-of-two images of at least 8 pixels")
+
+
+class _RawImages(Dataset):
+    """Decode (and, for `--resize pil`, crop and resize) in the loader's workers; no GPU is touched here.  The GPU path gets the
+    decoded pixels and their plan of passes (the coefficient tables), so the main process only concatenates tables."""
+
+    def __init__(self, paths, transform, resolution, resize):
+        self.paths, self.transform, self.resolution, self.resize = paths, transform, resolution, resize
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, i):
+        import PIL.Image
+        from . import resample
+        img = np.array(PIL.Image.open(self.paths[i]).convert("RGB"))
+        if self.resize == "pil":   # tensors travel from the workers through shared memory, arrays through a pipe
+            return torch.from_numpy(resample.pil_transform(img, self.transform, self.resolution)), None
+        return torch.from_numpy(img), resample.plan(img.shape[0], img.shape[1], self.transform, self.resolution)
+
+
+def _collate_list(items):
+    return items
+
+
+def convert_image_folder(source_dir, dest_dir, resolution, transform="center-crop-dhariwal", resize="pil", batch_size=64,
+                         max_images=None, num_workers=4, vae_sd_dest=None, vae_ckpt=None, precision="fp32", device="cuda",
+                         log_every=0):
+    """Write <dest_dir>/{00000/img00000000.png, ...} (uncompressed RGB PNGs, resolution x resolution) and <dest_dir>/dataset.json
+    for the images of `source_dir` (list_image_folder), cropped and resized as the reference's `convert --transform` does.
+    resize "gpu": Pillow's arithmetic on the HIP kernel (resample.center_crop_batch); "pil": Pillow in the workers; the files are
+    the same.  With `vae_sd_dest` and `vae_ckpt` every cropped batch also goes through the SD-VAE encoder and its moments are
+    written as `encode_image_folder` would write them from <dest_dir>.  The files do not depend on `batch_size`."""
+    import PIL.Image
+    check_convert_args(source_dir, dest_dir, resolution, transform)
+    if resize not in ("gpu", "pil"):
+        raise ValueError(f"--resize {resize}: gpu or pil")
+    if (vae_sd_dest is None) != (vae_ckpt is None):
+        raise ValueError("--vae-sd-dest and --vae-ckpt go together")
+    if vae_sd_dest is not None:
+        _check_folders(source_dir, vae_sd_dest)
+        if os.path.abspath(vae_sd_dest) == os.path.abspath(dest_dir):
+            raise ValueError(f"{vae_sd_dest}: the moments need a folder of their own")
+    items = list_image_folder(source_dir, max_images)
+    if not items:
+        raise ValueError(f"{source_dir}: no images")
+    if (resize == "gpu" or vae_sd_dest is not None) and not torch.cuda.is_available():
+        raise ValueError("no GPU: --resize gpu and --vae-sd-dest run on one (--resize pil needs none)")
+    vae = None
+    if vae_sd_dest is not None:
+        from .vae import load_sd_vae_encoder
+        vae = load_sd_vae_encoder(vae_ckpt, device=device)
+        os.makedirs(vae_sd_dest, exist_ok=True)
+    if resize == "gpu":
+        from .resample import center_crop_batch
+    os.makedirs(dest_dir, exist_ok=True)
+    loader = torch.utils.data.DataLoader(_RawImages([p for p, _ in items], transform, resolution, resize), batch_size=batch_size,
+                                         shuffle=False, num_workers=num_workers, collate_fn=_collate_list)
+    idx = 0
+    for batch in loader:
+        if resize == "gpu":
+            raw = center_crop_batch([im.numpy() for im, _ in batch], transform, resolution, device=device, plans=[p for _, p in batch])
+            pixels = raw.permute(0, 2, 3, 1).cpu().numpy()
+        else:
+            pixels = torch.stack([im for im, _ in batch]).numpy()
+            raw = torch.from_numpy(pixels).permute(0, 3, 1, 2).contiguous().to(device) if vae is not None else None
+        if vae is not None:
+            _write_moments(vae_sd_dest, idx, vae.encode(raw, precision=precision))
+        for hwc in pixels:
+            fn = os.path.join(dest_dir, image_fname(idx))
+            os.makedirs(os.path.dirname(fn), exist_ok=True)
+            PIL.Image.fromarray(np.ascontiguousarray(hwc)).save(fn, format="png", compress_level=0, optimize=False)
+            idx += 1
+        if log_every and idx % log_every < len(batch):
+            print(f"[dataset convert] {idx}/{len(items)}", flush=True)
+    if vae is not None:
+        _write_metadata(vae_sd_dest, moments_metadata(items))
+    return _write_metadata(dest_dir, image_metadata(items))
+
+
+# the faster of the two end to end in profiles/dataset_convert.txt (382 against 310 images/s: the main process, which writes the
+# PNGs, bounds both, and the GPU path gives it more to copy); the files are the same either way
+CONVERT_RESIZE_DEFAULT = "pil"
 
 
 def main(argv=None):
@@ -306,6 +431,25 @@ def main(argv=None):
     e.add_argument("--batch-size", type=int, default=8, help="images per encoder call (the files do not depend on it)")
     e.add_argument("--max-images", type=int, default=None)
     e.add_argument("--num-workers", type=int, default=4, help="PNG decode processes (at most 16)")
+    c = sub.add_parser("convert", help="crop and resize raw images into an image folder (images/), optionally with vae-sd/",
+                       description="Crop and resize every image under a folder (any sizes, any format Pillow opens) to RxR and write "
+                                   "them as the reference's `dataset_tools.py convert` does: <dest_images_dir>/00000/img00000000.png, "
+                                   "... (uncompressed PNG) and dataset.json with labels from <source_dir>/dataset.json or the "
+                                   "top-level directory names.  The pixels are Pillow's, bit for bit, on either --resize path. "
+                                   "Directories only; the destination must be empty or absent.")
+    c.add_argument("source_dir")
+    c.add_argument("dest_images_dir")
+    c.add_argument("--resolution", type=int, required=True, help="R: output is RxR, a power of two of at least 8")
+    c.add_argument("--transform", default="center-crop-dhariwal",
+                   help="center-crop-dhariwal (ADM's: BOX halvings, BICUBIC, centre crop; the default) or center-crop (crop, LANCZOS)")
+    c.add_argument("--resize", choices=["gpu", "pil"], default=CONVERT_RESIZE_DEFAULT,
+                   help="where the crop / resize runs: the HIP kernel, or Pillow in the workers (same files)")
+    c.add_argument("--batch-size", type=int, default=64, help="images per launch (the files do not depend on it)")
+    c.add_argument("--max-images", type=int, default=None)
+    c.add_argument("--num-workers", type=int, default=4, help="decode processes (at most 16)")
+    c.add_argument("--vae-sd-dest", default=None, help="also encode every cropped batch into SD-VAE moments here (needs --vae-ckpt)")
+    c.add_argument("--vae-ckpt", default=None, help="sd-vae-ft-{mse,ema}: a diffusers directory, .safetensors or .bin")
+    c.add_argument("--precision", choices=["fp32", "fp16", "bf16"], default="fp32", help="the encoder's GEMM operand type")
     a = ap.parse_args(argv)
     if a.cmd == "pack":
         m = pack_dataset(a.data_dir, a.out_dir, a.text_embeds_dir, a.features_dirs, with_images=not a.no_images, log_every=10000)
@@ -313,6 +457,15 @@ def main(argv=None):
         return
     if a.batch_size < 1 or (a.max_images is not None and a.max_images < 1) or not 0 <= a.num_workers <= 16:
         ap.error("--batch-size and --max-images must be at least 1, --num-workers in [0, 16]")
+    if a.cmd == "convert":
+        try:
+            meta = convert_image_folder(a.source_dir, a.dest_images_dir, a.resolution, transform=a.transform, resize=a.resize,
+                                        batch_size=a.batch_size, max_images=a.max_images, num_workers=a.num_workers,
+                                        vae_sd_dest=a.vae_sd_dest, vae_ckpt=a.vae_ckpt, precision=a.precision, log_every=10000)
+        except ValueError as err:
+            raise SystemExit(f"dataset convert: {err}")
+        print(json.dumps({"dest": a.dest_images_dir, "vae_sd_dest": a.vae_sd_dest, "labelled": meta["labels"] is not None}))
+        return
     try:
         meta = encode_image_folder(a.source_images_dir, a.dest_dir, a.vae_ckpt, precision=a.precision, batch_size=a.batch_size,
                                    max_images=a.max_images, num_workers=a.num_workers, log_every=10000)
@@ -324,3 +477,4 @@ def main(argv=None):
 
 if __name__ == "__main__":   # python -m reed_amd.dataset pack <data_dir> <out_dir> [--text-embeds-dir D] [--features-dirs A B] [--no-images]
     main()                   # python -m reed_amd.dataset encode <source_images_dir> <dest_dir> --vae-ckpt PATH [...]
+                             # python -m reed_amd.dataset convert <source_dir> <dest_images_dir> --resolution R [...]

@@ -666,3 +666,11 @@ def vae_image_rows(raw_u8, out, B, H, W, row0, nrows, kcols, ldo):
 def vae_moments(y, ldc, B, h, w, qw, qb, out):
     """out f32 [B, 8, h, w] = cat[mean, std] of quant_conv(y[:, :8]) (qw f32 [8, 8], qb f32 [8]), logvar clamped to [-30, 20]."""
     _call("reed_vae_moments", _p(y), ldc, B, h, w, _p(qw), _p(qb), _p(out), _stream())
+
+
+# ---------------- dataset convert: Pillow's 8-bit resampler (csrc/resample.hip) ----------------
+def resample_u8(src, dst, out, items, tile_prefix, n_items, total_tiles, coefs, bounds):
+    """One pass level of a ragged batch of RGB images (reed_resample_u8; tables: reed_amd/resample.py BatchPlan): horizontal and
+    vertical items write interleaved rows into `dst`, an image's last (vertical) pass its planar u8 [3, R, R] crop into `out`."""
+    _call("reed_resample_u8", _p(src), _p(dst), _p(out), _p(items), _p(tile_prefix), n_items, total_tiles, _p(coefs), _p(bounds),
+          _stream())
