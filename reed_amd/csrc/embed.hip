@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_kernel(const float* __res
       for (int j = 0; j < 8; ++j) {
         float wf = bf2f(wv[j]);
 #pragma unroll
-        for (int s = 0; s < 8; ++s) acc[s] += wf * xs[s * K + k + j];
+        for (int s = 0; s < 8; ++s) acc[s] = fmaf(wf, xs[s * K + k + j], acc[s]);   // fmaf spelled out: see patch_embed_fwd16_kernel
       }
     }
     const float bv = bias ? bf2f(bias[d]) : 0.f;
@@ -73,6 +73,10 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_kernel(const float* __res
 // 16-byte load of the positional row and ONE 16-byte store per token, where the kernel above re-reads every input of its 8 tokens
 // from LDS for every column (128 ds_read_b32 per column) and stores 4 bytes per lane.  Same accumulation order over k:
 // bit-identical tokens.  320 threads (288 of them active for D = 1152).
+// Both kernels spell the accumulation as fmaf: written as `acc += w * x` it is left to the compiler which products are fused, and
+// in the fp32 build (where a product of two operands is not exact) the kernel above came out with two of its eight token chains
+// as a multiply and an add, one rounding more per term than here: tokens that differed in the last place between the two forms
+// (tests/test_embed_gpu.py, fp32, (5, 4, 18, 2, 1280)).  In the 16-bit builds the products are exact either way.
 constexpr int PT = 64, PK = 16, PNT = 320;
 __global__ __launch_bounds__(PNT) void patch_embed_fwd16_kernel(const float* __restrict__ x, const bf16* __restrict__ w,
                                                                 const bf16* __restrict__ bias,
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(PNT) void patch_embed_fwd16_kernel(const float* __r
     for (int e = 0; e < 4; ++e) {
       float acc = 0.f;
 #pragma unroll
-      for (int k = 0; k < PK; ++k) acc += wr[e][k] * xv[k >> 2][k & 3];
+      for (int k = 0; k < PK; ++k) acc = fmaf(wr[e][k], xv[k >> 2][k & 3], acc);
       o[e] = bfround(acc + bv[e]) + pv[e];
     }
     *(f32x4*)(tok + bt * D + d0) = o;

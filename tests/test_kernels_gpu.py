@@ -189,6 +189,7 @@ def test_patch_embed_and_final_layer_index_maps_bit_exact(dev):
 
 
 def test_patch_embed_values_and_smallk_wgrad(dev):
+    """A first look at one size; tests/test_embed_gpu.py holds these kernels to fp64 budgets at the edge shapes in all three builds."""
     from reed_amd import ops
     B, C, HW, P, D = 3, 4, 16, 2, 384
     T, K = 64, 16
@@ -216,6 +217,7 @@ def test_patch_embed_values_and_smallk_wgrad(dev):
 
 
 def test_timestep_sinusoid_and_label_cond(dev):
+    """Against the golden table at one size; tests/test_embed_gpu.py holds these kernels to fp64 budgets at the edge shapes."""
     from reed_amd import ops
     gs = load("static")
     t = torch.from_numpy(gs["sinus_t"]).to(dev)
