@@ -81,9 +81,21 @@ int reed_planning_cus(void);
  * a whole CU per workgroup for their entire run (the persistent form of the 256x256 kernel) are then not selected. */
 int reed_set_concurrent_comm(int on);
 
-/* tile selection override for tests / A-B timing: 0 = heuristic (default), 128 or 256 = force that kernel, 144 = force
- * the 256x144 kernel wherever it applies (NT / NN, bf16-output epilogue, N % 144 == 0, no split-K) */
+/* tile selection override for tests / A-B timing: 0 = heuristic (default); 64 (skinny one-wave tiles) / 128 / 144 (256x144) / 256
+ * (256x256, eight waves) / 257 (256x256, four waves, one tile per workgroup) / 258 (the same, persistent wherever that form
+ * applies) / 288 (256x288) = that kernel wherever the shape allows, the heuristic elsewhere; 259 = heuristic plus the column split */
 int reed_gemm_force_tile(int tile);
+/* Dry run of reed_gemm's kernel selection (host arithmetic, no device call, no pointers: csrc/gemm_plan.cpp).  layout, epilogue,
+ * M, N, K, split_k and rows_per_gate as for reed_gemm; flags: 1 = dbias given, 2 = slab_stride > 0, 4 = R and C2 given.  The knobs
+ * are explicit: ncu = CUs to plan for (<= 0: reed_planning_cus()), forced_tile as for reed_gemm_force_tile, colsplit / use288 = the
+ * switches REED_GEMM_COLSPLIT / REED_GEMM288 (< 0: as the environment set them at load), concurrent_comm as for
+ * reed_set_concurrent_comm.  Returns the number of launches n <= 3 and fills launches[9 n] (NULL: count only) with, per launch,
+ * {kernel, row0, rows, col0, cols, splits, ksplit_len, tile_gm, grid}: kernel 0 = 128x128 tiles, 1 = 256x144, 2 = 256x288, 3 = 256x256
+ * eight waves, 4 = 256x256 four waves one-shot, 5 = the same persistent, 6 = skinny, 7 = TN 256x128, 8 = TN 128x256, 9 = the
+ * fp32-operand library's one kernel; the launch computes rows [row0, row0 + rows) x columns [col0, col0 + cols) of the output with
+ * grid.x = grid, grid.y = splits.  Where reed_gemm would refuse the shape: minus its error code (-1001 / -1002). */
+int reed_gemm_plan(int layout, int epilogue, int M, int N, int K, int split_k, int flags, int rows_per_gate, int ncu,
+                   int forced_tile, int colsplit, int use288, int concurrent_comm, int* launches);
 
 /* bias gradient: out[n] (+)= sum_m x[m,n], x bf16 [M,N] (row stride ld); ws: caller scratch of
  * reed_colsum_ws_floats(M, N) floats. Deterministic (fixed reduction order). */

@@ -61,12 +61,12 @@ extern "C" int reed_gemm(int layout, int epilogue, const void* P, int64_t ldp, c
   if (epilogue == EPI_RES_BF16) REED_CHECK_ARG(R, "reed_gemm: residual epilogue needs R");
   if (epilogue == EPI_GATE_RES) REED_CHECK_ARG(R && gate, "reed_gemm: gate-residual epilogue needs R and gate");
   if (epilogue == EPI_LS_RES)
-    REED_CHECK_ARG(R && gate && layout == LAY_NT && split_k <= 1, "reed_gemm: LayerScale-residual epilogue: NT, R and gamma (gate)");
+    REED_CHECK_ARG(R && gate && epi_layout_ok(layout, epilogue, N, split_k), "reed_gemm: LayerScale-residual epilogue: NT, R and gamma (gate)");
   if (epilogue == EPI_SWIGLU) {
 #if defined(REED_FP32)
     REED_CHECK_ARG(false, "reed_gemm: the SwiGLU epilogue (17) is not part of the fp32-operand build (the frozen towers run on the bf16 library)");
 #endif
-    REED_CHECK_ARG(layout == LAY_NT && split_k <= 1 && C && N % 128 == 0 && ldc >= N / 2,
+    REED_CHECK_ARG(epi_layout_ok(layout, epilogue, N, split_k) && C && ldc >= N / 2,
                    "reed_gemm: SwiGLU epilogue: NT on the packed weight, no split-K, C [M, N/2] given, N=%d a multiple of 128, ldc=%ld >= N/2",
                    N, (long)ldc);
   }

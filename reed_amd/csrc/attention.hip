@@ -2737,8 +2737,8 @@ int set_lds(K kernel, int bytes) {
 }
 
 }  // namespace
-int reed_concurrent_comm();   // gemm256.hip
-int reed_num_cus();           // gemm256.hip: the device's CUs minus the reserve (reed_set_cu_reserve) — the persistent kernels' grids
+int reed_concurrent_comm();   // gemm_plan.cpp
+int reed_num_cus();           // gemm_plan.cpp: the device's CUs minus the reserve (reed_set_cu_reserve) — the persistent kernels' grids
                               // leave the reserved CUs to whatever the caller runs beside them (RCCL channels; a co-running kernel)
 namespace {
 int num_cus() { return reed_num_cus(); }

@@ -38,6 +38,52 @@ enum {
 };
 constexpr int SWIGLU_GROUP = 8;   // = the 8 columns a lane of tile_epilogue owns: the partner sits in the neighbouring lane
 
+// Sets of epilogues as bit masks over the EPI_* values: every "which epilogues" question of the selection (gemm_plan.cpp) has
+// its one answer here.
+template <class... E>
+constexpr unsigned epi_set(E... e) { return ((1u << e) | ...); }
+constexpr bool epi_in(unsigned set, int epi) { return epi >= 0 && epi < 32 && ((set >> epi) & 1u) != 0; }
+// -- per kernel and layout: has an instantiation / is allowed
+// the bf16-output epilogues, all built for the 256x144 tile
+constexpr unsigned EPIS_144 = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_QGELU, EPI_GELU_ERF,
+                                      EPI_RES_BF16, EPI_GELU_G, EPI_SILU_G, EPI_MUL);
+// the 256x288 tile: the epilogues of the two 4608-wide GEMMs it was built for (fc1 forward, fc2 input gradient)
+constexpr unsigned EPIS_288 = epi_set(EPI_BF16, EPI_GELU, EPI_GELU_G, EPI_DGELU, EPI_MUL);
+// the skinny tiles: the row-free bf16 / fp32-residual epilogues of a frozen tower's forward (NT).  Against EPIS_144: + LS_RES,
+// SWIGLU (tower epilogues); - DGELU, DSILU, MUL: as found (a forward has none of them)
+constexpr unsigned EPIS_SKINNY = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_QGELU, EPI_GELU_ERF, EPI_GELU_G, EPI_SILU_G, EPI_RES_BF16,
+                                         EPI_LS_RES, EPI_GATE_RES, EPI_SWIGLU);
+// the four-wave 256^2 kernel.  QuickGELU / exact-GELU are built for it and NOT eligible: they stay on the 8-wave kernel — their
+// VALU work (erff, two roundings per element) needs two waves per SIMD to hide its own latency; measured 0.93 vs 0.64 ms on the
+// ViT-L fc1 shape.  DSILU is missing from the NT set as found.
+constexpr unsigned EPIS_256W_NT = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_GELU_G, EPI_SILU_G, EPI_RES_BF16, EPI_LS_RES,
+                                          EPI_BF16_DOT, EPI_DGELU, EPI_MUL, EPI_SWIGLU);
+// input gradients on the weights as they are: the backward's epilogues only
+constexpr unsigned EPIS_256W_NN = epi_set(EPI_BF16, EPI_BF16_DOT, EPI_DGELU, EPI_DSILU, EPI_MUL);
+// the 256^2 kernels' re-dealt ragged last column tile (<= 128 live columns) counts ~0.6 of a tile in the cost model for these:
+// the bf16-output epilogues = EPIS_144, + LS_RES, SWIGLU as found
+constexpr unsigned EPIS_RAGGED_COL = EPIS_144 | epi_set(EPI_LS_RES, EPI_SWIGLU);
+// the 128^2 and eight-wave 256^2 kernels build every epilogue but 13; LS_RES and SWIGLU for NT only, and the eight-wave kernel
+// on TN the fp32 outputs only (weight gradients)
+constexpr unsigned EPIS_NT_ONLY = epi_set(EPI_LS_RES, EPI_SWIGLU);
+// (reed_gemm refuses them elsewhere, with split-K, and SWIGLU for N not a multiple of 128, before any selection: api.cpp)
+constexpr bool epi_layout_ok(int layout, int epi, int N, int split_k) {
+  return !epi_in(EPIS_NT_ONLY, epi) || (layout == LAY_NT && split_k <= 1 && (epi != EPI_SWIGLU || N % 128 == 0));
+}
+constexpr unsigned EPIS_128_NT = (1u << 18) - 1u - epi_set(EPI_BF16_DOT);
+constexpr unsigned EPIS_256X8_TN = epi_set(EPI_F32, EPI_ADDF32_RB, EPI_ATOMIC_F32);
+// -- semantic
+// the row index carries no meaning (rows may go out as two launches): EPIS_RAGGED_COL - GATE_RES (the gate is per sample =
+// per block of rows); the head-dot slots of epilogue 13 and the fp32 outputs are left alone
+constexpr unsigned EPIS_ROWS_FREE = EPIS_RAGGED_COL & ~epi_set(EPI_GATE_RES);
+// the column index carries no meaning beyond the offsets the launcher applies to Q / C / C2 / R / bias / gate (columns may go
+// out as two launches): = EPIS_144.  Against EPIS_ROWS_FREE: + GATE_RES (its gate is per row block, not per column); - LS_RES,
+// SWIGLU: as found (the launcher offsets `gate` as 16-bit elements, LS_RES's is an fp32 vector; SWIGLU's output has N / 2 columns)
+constexpr unsigned EPIS_COLS_FREE = EPIS_144;
+// bytes per element of C and of R: the two fp32-residual epilogues have fp32 outputs; the splits take bf16 for everything else
+// in their sets
+constexpr int epi_out_bytes(int epi) { return epi == EPI_GATE_RES || epi == EPI_LS_RES ? 4 : 2; }
+
 struct GemmArgs {
   const bf16* P;
   const bf16* Q;

@@ -21,7 +21,8 @@
 // before this half's MFMAs:
 //   half 0:  wait reads(t, ks0) | issue reads(t, ks1) | MFMA(t, ks0)
 //   half 1:  wait DMA(t+1), reads(t, ks1) | barrier | issue DMA(t+3) into t's slot | issue reads(t+1, ks0) | MFMA(t, ks1)
-// NT / NN layouts, bf16-output epilogues (tile_epilogue's LDS-staged row-contiguous stores), no split-K.
+// NT / NN layouts, bf16-output epilogues (tile_epilogue's LDS-staged row-contiguous stores), no split-K.  Which shapes run here
+// is gemm_plan.cpp's decision (cost144 / prefer144); this file holds the kernel and its launcher.
 #include <math.h>
 #include <stdlib.h>
 
@@ -394,45 +395,7 @@ int dispatch144(int epi, const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// shapes the 256x144 kernel can take: NT / NN, bf16-output epilogue, N a multiple of 144, no split-K
-bool reed_gemm144_eligible(int layout, int epi, const GemmArgs& a, int splits) {
-  const bool bf16_epi = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_GATE_RES || epi == EPI_DGELU ||
-                        epi == EPI_DSILU || epi == EPI_QGELU || epi == EPI_GELU_ERF || epi == EPI_RES_BF16 || epi == EPI_GELU_G ||
-                        epi == EPI_SILU_G || epi == EPI_MUL;
-  return (layout == LAY_NT || layout == LAY_NN) && bf16_epi && splits <= 1 && a.N % BN4 == 0 && a.K % BK4 == 0 &&
-         a.K >= BK4;
-}
-
-int reed_num_cus();   // gemm256.hip
-double reed_gemm256_rate();
-
-// Kernel selection against the 256^2 / 128^2 kernels, in gemm256.hip's units (one CU x one 128^2 tile; 256^2 tile = 4 /
-// 1.18).  A 256x144 tile is 0.5625 of a 256^2 tile; with the loader waves its main loop runs at the chip's dense-MFMA
-// ceiling when all 256 CUs are busy, but per round it exposes the same epilogue as the 256^2 kernel on 0.56 of the work,
-// so over the block shapes it is worth ~0.92 of the 256^2 kernel per flop (tools/tile_ab.py and, in-step,
-// a sweep of the threshold inside the step, b = 32 .. 256, round 2): cost = rounds x 2.25 / 0.92.  The 256^2 side: below two rounds in WHOLE rounds
-// (ragged column tiles as workgroups: at 1.25 rounds — b = 64, N = 1152 — the second, quarter-full round costs a full
-// tile time), from two rounds on gemm256.hip's own half-round model.  Outcome on SiT-XL/2: the five 1152-wide outputs
-// (proj / fc2 forward, dgrads of qkv / proj / fc1) at b <= 64 per GPU and the two 4608-wide ones (fc1 forward, fc2
-// dgrad) at b = 32; everything else stays where it was.
-bool reed_gemm144_preferred(int layout, int epi, const GemmArgs& a, int splits) {
-  if (!reed_gemm144_eligible(layout, epi, a, splits) || a.K < 256) return false;
-  const int ncu = reed_num_cus();
-  constexpr double eta = 0.92;
-  const long tm = cdiv(a.M, 256), tn = cdiv(a.N, 256);
-  const long t144 = (long)cdiv(a.M, BM4) * (a.N / BN4);
-  const long t128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
-  double r256 = (double)((tm * tn + ncu - 1) / ncu);
-  if ((a.N % 256) != 0 && (a.N % 256) <= 128) {
-    const double w = (double)tm * (tn - 1) + 0.6 * tm;
-    if (w >= 2.0 * ncu) r256 = ceil(2.0 * w / ncu) / 2.0;
-  }
-  const double c144 = (double)((t144 + ncu - 1) / ncu) * 2.25 / eta;
-  const double c256 = r256 * 4.0 / reed_gemm256_rate();
-  const double c128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * 2.0;
-  return c144 < c256 && c144 < c128;
-}
-
+// (shapes: NT / NN, an epilogue of EPIS_144, N a multiple of 144, no split-K; when it is preferred: gemm_plan.cpp)
 int reed_gemm144_launch(int layout, int epi, GemmArgs a, hipStream_t stream) {
   if (layout == LAY_NT) return dispatch144<LAY_NT>(epi, a, stream);
   return dispatch144<LAY_NN>(epi, a, stream);

@@ -14,6 +14,7 @@
 //   p3      Q(1,0)  A1r,B0r    A-mh0,B-nh0(t+1)    (next p0)   A0(t+2)      [vmcnt(4) + barrier first]
 // Each phase starts with s_waitcnt lgkmcnt(0) + s_barrier, which orders (WAR) the reads of a half-tile before the
 // DMA that overwrites it two K-tiles later, and (RAW, at p3) the landed K-tile t+1 before its first fragment read.
+// Which shapes run here is gemm_plan.cpp's decision (cost256 / prefer256); this file holds the kernel and its launcher.
 #include <math.h>
 #include <stdlib.h>
 
@@ -326,9 +327,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs a) {
     gemm256_body<LAY, EPI, false>(a, smem, tm, tn);
 }
 
-// Tile rows per group of the XCD-local tile walk (kernel: groups of GM tile rows x all tile columns, rows fastest).
-int tile_group_rows(const GemmArgs& a) { return 4; }
-
 template <int LAY, int EPI>
 int launch256(const GemmArgs& a, int splits, hipStream_t stream) {
   static bool attr_set = false;
@@ -339,9 +337,7 @@ int launch256(const GemmArgs& a, int splits, hipStream_t stream) {
     attr_set = true;
   }
   dim3 grid(cdiv(a.M, BM2) * cdiv(a.N, BN2), splits, 1);
-  GemmArgs b = a;
-  b.tile_gm = tile_group_rows(a);
-  REED_KLAUNCH((gemm256_kernel<LAY, EPI>), grid, dim3(512), LDS_BYTES, stream, b);
+  REED_KLAUNCH((gemm256_kernel<LAY, EPI>), grid, dim3(512), LDS_BYTES, stream, a);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }
@@ -385,64 +381,7 @@ int dispatch256(int epi, const GemmArgs& a, int splits, hipStream_t s) {
 
 }  // namespace
 
-// CUs the tile heuristics plan for = the device's count minus a reserve (reed_set_cu_reserve).  While a
-// gradient bucket is in flight RCCL's channels hold CUs, and a grid planned as exactly one round of the 256 CUs — the 256x144
-// tile at b = 32 per GPU, the grouped weight gradients' 512 slots — turns into two rounds on what is left.  The data-parallel
-// train step measures a few reserves during its first steps and keeps the fastest (reed_amd/trainer.py).
-static int g_cu_reserve = 0;
-extern "C" int reed_set_cu_reserve(int n) { g_cu_reserve = n > 0 ? n : 0; return 0; }
-int reed_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n - g_cu_reserve > 32 ? n - g_cu_reserve : 32;
-}
-extern "C" int reed_planning_cus(void) { return reed_num_cus(); }
-// Collectives run beside the GEMMs (a data-parallel step): kernels that need a whole CU per workgroup for their whole run
-// (the persistent form of gemm256w.hip) lose more than they gain when RCCL's channels hold some CUs — the workgroups that
-// find no CU start when another finishes its entire list.  The one-shot kernels degrade gracefully; they are used then.
-static int g_concurrent_comm = 0;
-extern "C" int reed_set_concurrent_comm(int on) { g_concurrent_comm = on ? 1 : 0; return 0; }
-int reed_concurrent_comm() { return g_concurrent_comm; }
-
-// Kernel selection (NT forward / NN dgrad), a round-count model fitted to A/B timing at the SiT-XL/2 shapes for b = 64
-// and 256 per GPU (tools/stagger_sweep.py): the 256^2 kernel does one tile per CU at a time and is ~1.18x faster per
-// flop (half the global->LDS bytes, deeper pipeline); the 128^2 kernel keeps two tiles per CU in flight, which
-// quantises better when the 256^2 grid is only one or two rounds.  Time in units of "one CU, one 128^2 tile":
-//   t256 = ceil(tiles256 / CUs) * 4 / 1.18        t128 = ceil(tiles128 / (2 CUs)) * 2
-// TN (wgrad) stays on the 128^2 kernel with wave-quantised split-K (ops.plan_wgrad); its 256^2 variant is reachable
-// through reed_gemm_force_tile only.
-// speed of the 256^2 kernel per flop relative to the 128^2 one in the round-count models
-double reed_gemm256_rate() { return 1.18; }
-
-bool reed_gemm256_preferred(int layout, int epi, const GemmArgs& a, int splits) {
-  if (layout == LAY_TN || splits > 1 || a.K < 256) return false;
-  const int ncu = reed_num_cus();
-  const long tm = cdiv(a.M, BM2), tn = cdiv(a.N, BN2);
-  // a ragged last column tile (<= 128 live columns; bf16-output epilogues) runs the re-dealt two-phase body: ~0.6 of a
-  // full tile, and such tiles fill the tail of the last round — count rounds in halves when there are any
-  // (A/B at b = 128: fc2 forward 0.407 -> 0.362 ms, fc1 / qkv dgrads 0.385 -> 0.322 / 0.285 -> 0.237 ms on 256^2)
-  const bool ragged = (a.N % BN2) != 0 && (a.N % BN2) <= 128 &&
-                      (epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_GATE_RES || epi == EPI_DGELU ||
-                       epi == EPI_DSILU || epi == EPI_QGELU || epi == EPI_GELU_ERF || epi == EPI_RES_BF16 || epi == EPI_LS_RES ||
-                       epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_MUL || epi == EPI_SWIGLU);
-  double rounds256;
-  if (ragged) {
-    const double w = (double)tm * (tn - 1) + 0.6 * tm;
-    rounds256 = ceil(2.0 * w / ncu) / 2.0;
-  } else {
-    rounds256 = (double)((tm * tn + ncu - 1) / ncu);
-  }
-  const long t128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
-  const double c256 = rounds256 * 4.0 / reed_gemm256_rate();
-  const double c128 = (double)((t128 + 2 * ncu - 1) / (2 * ncu)) * 2.0;
-  return c256 < c128;
-}
-
+// (which shapes run here, and the tile rows per group of the walk — GemmArgs::tile_gm —, is decided in gemm_plan.cpp)
 int reed_gemm256_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t stream) {
   switch (layout) {
     case LAY_NT: return dispatch256<LAY_NT>(epi, a, splits, stream);

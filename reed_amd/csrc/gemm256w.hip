@@ -16,6 +16,8 @@
 //   phase B  K-tile t+1 landed (vmcnt) + barrier: every wave is done reading K-tile t;
 //            issue the 16 reads of (t+1, ks0); 64 MFMAs on (t, ks1) with the 16 DMAs of K-tile t+2 (into the buffer
 //            K-tile t just left) spread between them, one per 4 MFMAs
+// The one-shot / persistent decision and the tile walk's group rows are gemm_plan.cpp's (w_persistent, w_tile_group_rows); this
+// file holds the kernels, their launcher and the grouped weight gradients.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,10 +27,8 @@
 #include <type_traits>
 
 #include "gemm_common.hpp"
+#include "gemm_plan.h"
 
-int reed_num_cus();   // gemm256.hip
-int reed_gemm_forced_tile();  // gemm.hip
-int reed_concurrent_comm();   // gemm256.hip
 
 #if defined(REED_CLK_PROBE) || defined(REED_CLK_PHASE)
 // diagnostic build only (tools/_ab/build_variant.py clk -DREED_CLK_PROBE, read by tools/clk_probe.py): shader-clock and
@@ -953,136 +953,50 @@ __global__ __launch_bounds__(256, 1) void gemm256w_tn_group_kernel(TnGroupW g) {
   }
 }
 
-// Tile rows per XCD-local group of the workgroup -> tile map (as gemm256.hip).
-// Measured at b = 256 (tools/_ab/gm_w4.sh): the 1152-wide outputs (4.5 column tiles) prefer groups of 2 rows — fc2 forward
-// 0.637 -> 0.618 ms, fc1 / qkv dgrads 0.564 -> 0.546 / 0.430 -> 0.417 —, the 3456- / 4608-wide ones groups of 4 (fc1 forward
-// 0.684 vs 0.720 with 2).
-int w_tile_group_rows(const GemmArgs& a) {
-#ifdef REED_TILE_GM_ENV   // diagnostic build only (tools/r6/gm_sweep.sh): the tile rows per XCD-local group from the environment
-  if (const char* e = getenv("REED_TILE_GM")) return atoi(e) > 0 ? atoi(e) : 4;
-#endif
-  if (cdiv(a.M, WBM) < 192) return 4;   // b = 128: 1157 (4 everywhere) vs 1151 images/s with the per-shape choice
-  const int ntn = cdiv(a.N, WBN);
-  return ntn <= 6 ? 2 : ntn >= 16 ? 5 : 4;   // (4608-wide: fc1 forward 0.688 -> 0.675, fc2 dgrad 0.727 -> 0.721 with 5)
-}
-
-// Static deal of the persistent form: the heaviest workgroup's load in full-tile units (a ragged tile counts RAG_COST) when
-// wpx workgroups per XCD take positions s, s + wpx, ... of their XCD's run.
-constexpr double RAG_COST = 0.58;
-double w_static_max_load(int ntm, int ntn, bool rag, int GM, int wpx) {
-  const int nwg = ntm * ntn, q = nwg >> 3, r = nwg & 7;
-  double worst = 0;
-  for (int xcd = 0; xcd < 8; ++xcd) {
-    const int run0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, runlen = q + (xcd < r ? 1 : 0);
-    for (int s = 0; s < wpx && s < runlen; ++s) {
-      double load = 0;
-      for (int p = s; p < runlen; p += wpx) {
-        const int b = run0 + p, per_group = GM * ntn, group = b / per_group, first_m = group * GM;
-        const int gs = std::min(ntm - first_m, GM), tn = (b % per_group) / gs;
-        load += (rag && tn == ntn - 1) ? RAG_COST : 1.0;
-      }
-      worst = std::max(worst, load);
-    }
-  }
-  return worst;
-}
-
-// mode 0: never (beside a collective; forced tile 257), 1: where the static deal is balanced (the default), 2: wherever the
-// form applies (forced tile 258: tests)
+// One tile per workgroup, or (persistent) `grid` = one workgroup per CU walking a static list of tiles: which form, the grid and
+// the tile rows per XCD-local group (GemmArgs::tile_gm) are gemm_plan.cpp's decision.
 template <int LAY, int EPI>
-int launch256wp(const GemmArgs& a, hipStream_t stream, bool* used) {
-  const int forced = reed_gemm_forced_tile();   // tests: 257 = the one-shot kernel, 258 = this form wherever it applies
-  const int mode = forced == 257 ? 0 : forced == 258 ? 2 : reed_concurrent_comm() ? 0 : 1;
-  *used = false;
-  const int nt = cdiv(a.K, WBK), ntm = cdiv(a.M, WBM), ntn = cdiv(a.N, WBN);
-  const int wpx = reed_num_cus() / 8;
-  if (mode == 0 || (nt & 1) || nt < 4 || wpx < 1 || (a.K % WBK) != 0) return REED_OK;
-  const bool rag = (a.N % WBN) != 0;
-  const int GM = w_tile_group_rows(a);
-  const double total = (double)ntm * ((ntn - (rag ? 1 : 0)) + (rag ? RAG_COST : 0.0));
-  const double ideal = total / (8.0 * wpx);
-  if (mode == 1 && ideal < 3.0) return REED_OK;       // too few tiles per workgroup for the hand-over to matter
-  if (mode == 1) {
-    // the verdict per (tile grid, group rows, workgroups per XCD) is remembered: the walk below is ~5 k steps on the host
-    static thread_local struct { int ntm, ntn, gm, wpx, ok; } memo[8];   // ntn carries the ragged flag in its sign
-    static thread_local int memo_n = 0;
-    int ok = -1;
-    for (int i = 0; i < memo_n; ++i)
-      if (memo[i].ntm == ntm && memo[i].ntn == (rag ? -ntn : ntn) && memo[i].gm == GM && memo[i].wpx == wpx) ok = memo[i].ok;
-    if (ok < 0) {
-      const double worst = w_static_max_load(ntm, ntn, rag, GM, wpx);
-      // the greedy hand-out of the one-shot kernel ends about half a tile after the balanced time when ragged tiles are mixed in
-      const double greedy = ideal + (rag ? 0.45 : 0.0);
-      ok = worst > greedy + 0.05 ? 0 : 1;
-      memo[memo_n % 8] = {ntm, rag ? -ntn : ntn, GM, wpx, ok};
-      if (memo_n < 8) ++memo_n;
-    }
-    if (!ok) return REED_OK;
-  }
+int launch256w(const GemmArgs& a, bool persistent, int grid, hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm256wp_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_W);
-    if (e != hipSuccess) { reed_set_error("gemm256wp: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
-  GemmArgs b = a;
-  b.tile_gm = GM;
-  REED_KLAUNCH((gemm256wp_kernel<LAY, EPI>), dim3(8 * wpx), dim3(256), LDS_W, stream, b);
-  REED_LAUNCH_CHECK();
-  *used = true;
-  return REED_OK;
-}
-
-template <int LAY, int EPI>
-int launch256w(const GemmArgs& a, hipStream_t stream) {
-  {
-    bool used = false;
-    const int rc = launch256wp<LAY, EPI>(a, stream, &used);
-    if (rc != REED_OK || used) return rc;
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm256w_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS_W);
+    hipError_t e = hipFuncSetAttribute((const void*)gemm256wp_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm256w_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W);
     if (e != hipSuccess) { reed_set_error("gemm256w: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
     attr_set = true;
   }
-  dim3 grid(cdiv(a.M, WBM) * cdiv(a.N, WBN), 1, 1);
-  GemmArgs b = a;
-  b.tile_gm = w_tile_group_rows(a);
-  REED_KLAUNCH((gemm256w_kernel<LAY, EPI>), grid, dim3(256), LDS_W, stream, b);
+  if (persistent) REED_KLAUNCH((gemm256wp_kernel<LAY, EPI>), dim3(grid), dim3(256), LDS_W, stream, a);
+  else REED_KLAUNCH((gemm256w_kernel<LAY, EPI>), dim3(grid), dim3(256), LDS_W, stream, a);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }
 
 template <int LAY>
-int dispatch256w(int epi, const GemmArgs& a, hipStream_t s) {
+int dispatch256w(int epi, const GemmArgs& a, bool persistent, int grid, hipStream_t s) {
   if constexpr (LAY == LAY_NT) {   // forward GEMMs: SiT blocks, the projector MLP, the frozen towers
     switch (epi) {
-      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, s);
-      case EPI_GELU: return launch256w<LAY, EPI_GELU>(a, s);
-      case EPI_SILU: return launch256w<LAY, EPI_SILU>(a, s);
-      case EPI_GELU_G: return launch256w<LAY, EPI_GELU_G>(a, s);
-      case EPI_SILU_G: return launch256w<LAY, EPI_SILU_G>(a, s);
-      case EPI_GATE_RES: return launch256w<LAY, EPI_GATE_RES>(a, s);
-      case EPI_RES_BF16: return launch256w<LAY, EPI_RES_BF16>(a, s);
-      case EPI_LS_RES: return launch256w<LAY, EPI_LS_RES>(a, s);
-      case EPI_QGELU: return launch256w<LAY, EPI_QGELU>(a, s);
-      case EPI_GELU_ERF: return launch256w<LAY, EPI_GELU_ERF>(a, s);
-      case EPI_SWIGLU: return launch256w<LAY, EPI_SWIGLU>(a, s);
+      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, persistent, grid, s);
+      case EPI_GELU: return launch256w<LAY, EPI_GELU>(a, persistent, grid, s);
+      case EPI_SILU: return launch256w<LAY, EPI_SILU>(a, persistent, grid, s);
+      case EPI_GELU_G: return launch256w<LAY, EPI_GELU_G>(a, persistent, grid, s);
+      case EPI_SILU_G: return launch256w<LAY, EPI_SILU_G>(a, persistent, grid, s);
+      case EPI_GATE_RES: return launch256w<LAY, EPI_GATE_RES>(a, persistent, grid, s);
+      case EPI_RES_BF16: return launch256w<LAY, EPI_RES_BF16>(a, persistent, grid, s);
+      case EPI_LS_RES: return launch256w<LAY, EPI_LS_RES>(a, persistent, grid, s);
+      case EPI_QGELU: return launch256w<LAY, EPI_QGELU>(a, persistent, grid, s);
+      case EPI_GELU_ERF: return launch256w<LAY, EPI_GELU_ERF>(a, persistent, grid, s);
+      case EPI_SWIGLU: return launch256w<LAY, EPI_SWIGLU>(a, persistent, grid, s);
       // round 6: the input gradients as NT GEMMs on a transposed copy of the weights (engine.py: both operands k-contiguous)
-      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, s);
-      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, s);
-      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, s);
+      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, persistent, grid, s);
+      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, persistent, grid, s);
+      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, persistent, grid, s);
     }
   } else {                         // input gradients (on the weights as they are: k-strided B operand)
     switch (epi) {
-      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, s);
-      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, s);
-      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, s);
-      case EPI_DSILU: return launch256w<LAY, EPI_DSILU>(a, s);
-      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, s);
+      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, persistent, grid, s);
+      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, persistent, grid, s);
+      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, persistent, grid, s);
+      case EPI_DSILU: return launch256w<LAY, EPI_DSILU>(a, persistent, grid, s);
+      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, persistent, grid, s);
     }
   }
   reed_set_error("reed_gemm(256w): epilogue %d not built for this layout", epi);
@@ -1091,22 +1005,11 @@ int dispatch256w(int epi, const GemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-bool reed_gemm256w_eligible(int layout, int epi, const GemmArgs& a, int splits) {
-  // (QuickGELU / exact-GELU epilogues stay on the 8-wave kernel: their VALU work — erff, two roundings per element — needs two
-  // waves per SIMD to hide its own latency; measured 0.93 vs 0.64 ms on the ViT-L fc1 shape)
-  const bool epi_ok = layout == LAY_NT ? (epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_GATE_RES ||
-                                          epi == EPI_GELU_G || epi == EPI_SILU_G || epi == EPI_RES_BF16 || epi == EPI_LS_RES ||
-                                          epi == EPI_BF16_DOT || epi == EPI_DGELU || epi == EPI_MUL || epi == EPI_SWIGLU)
-                                       : (epi == EPI_BF16 || epi == EPI_BF16_DOT || epi == EPI_DGELU || epi == EPI_DSILU || epi == EPI_MUL);
-  return (layout == LAY_NT || layout == LAY_NN) && splits <= 1 && a.K % WBK == 0 && a.K >= 2 * WBK && a.N % 128 == 0 && epi_ok;
+// (eligible shapes and epilogues — EPIS_256W_NT / EPIS_256W_NN, fewer than are built above —: gemm_plan.cpp, gemm.h)
+int reed_gemm256w_launch(int layout, int epi, GemmArgs a, bool persistent, int grid, hipStream_t stream) {
+  if (layout == LAY_NT) return dispatch256w<LAY_NT>(epi, a, persistent, grid, stream);
+  return dispatch256w<LAY_NN>(epi, a, persistent, grid, stream);
 }
-
-int reed_gemm256w_launch(int layout, int epi, GemmArgs a, hipStream_t stream) {
-  if (layout == LAY_NT) return dispatch256w<LAY_NT>(epi, a, stream);
-  return dispatch256w<LAY_NN>(epi, a, stream);
-}
-
-int reed_gemm_forced_tile();  // gemm.hip
 
 // The deal of the grouped weight gradients (TnGroupW): n problems dw_i [M_i, N_i] with or without a bias gradient on `ncu` CUs.
 // Fills item[256] in the kernel's layout (XCD x, workgroup j of it -> item[x * (ncu / 8) + j]; 0xFFFFFFFF = none) and returns the

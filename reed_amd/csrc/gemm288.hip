@@ -3,8 +3,8 @@
 // image/models/sit.py:121-124 through timm's Mlp).  M = 8192 x N = 4608 is 2.25 rounds of 256^2 tiles (three rounds run) and four
 // rounds of 256x144 tiles, whose K loop is bound by the L2 -> LDS operand stream (50 KiB per K-tile and CU: gemm144.hip); a 256x288
 // tile moves 68 KiB per K-tile for twice the products — 1.47 x the FLOP per operand byte — and 4608 = 16 x 288, 8192 = 32 x 256:
-// 512 workgroups.  BUILT AS VERDICT round 5 ASKED (item 3a), BIT-IDENTICAL TO THE 256x144 KERNEL, AND MEASURED NOT FASTER: see "Selection"
-// at the end of this file and profiles/r6_gemm288.txt — the heuristic does not take it.
+// 512 workgroups.  BUILT AS VERDICT round 5 ASKED (item 3a), BIT-IDENTICAL TO THE 256x144 KERNEL, AND MEASURED NOT FASTER: see the note
+// at the end of this file and profiles/r6_gemm288.txt — the heuristic (gemm_plan.cpp) does not take it.
 //
 // 8 waves = 4 (rows) x 2 (columns): wave (wr, wc) owns rows 64 wr .. + 63 and columns 144 wc .. + 143 = 4 x 9 MFMA tiles (144
 // accumulator registers).  Two waves per SIMD (w and w + 4) and 256 registers each leave no room for double-buffered fragments of a
@@ -232,43 +232,15 @@ int launch288(const GemmArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// shapes the 256x288 kernel can take: NT, one of its epilogues, N a multiple of 288, K of 64, no split-K
-bool reed_gemm288_eligible(int layout, int epi, const GemmArgs& a, int splits) {
-  const bool epi_ok = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_GELU_G || epi == EPI_DGELU || epi == EPI_MUL;
-  return layout == LAY_NT && epi_ok && splits <= 1 && a.N % BN8 == 0 && a.K % BK8 == 0 && a.K >= 2 * BK8;   // (>= 4 k-steps: the prologue stages three)
-}
-
-int reed_num_cus();   // gemm256.hip
-double reed_gemm256_rate();
-
-// Selection.  MEASURED (profiles/r6_gemm288.txt): the kernel is bit-identical to the 256x144 kernel and NOT faster — 8192 tokens x 4608
+// Shapes: NT, an epilogue of EPIS_288, N a multiple of 288, K of 64 and >= 128, no split-K (gemm_plan.cpp).
+// MEASURED (profiles/r6_gemm288.txt): the kernel is bit-identical to the 256x144 kernel and NOT faster — 8192 tokens x 4608
 // columns 99-101 us (two rounds) against 97-100 (four rounds of 256x144) and 100 (three of 256^2); one round (4096 tokens) 46-52 us
 // against 51-53.  With its parts switched off, one round of plain stores: launch + prologue 5.8 us, epilogue 6.3, the K loop 30 (MFMAs
 // alone 17.3 = the matrix pipe's floor at the 2.4 GHz the chip holds under this kernel; the loop with nothing in it 6.3: 36 barriers;
 // the DMAs alone 12; the fragment reads 4.4) — with two waves per SIMD running the same program between barriers the parts add up
 // more than they overlap.  The ring that lets the DMA run ahead costs a barrier per 32-wide k-step, and with whole K-tiles of 128-byte
 // rows only two 68 KiB stages fit the 160 KiB (the first form: the same 50 us per round).  So the heuristic does NOT take it
-// (REED_GEMM288=1 does, in gemm144.hip's units: 4.5 of area at REED_GEMM288_ETA of the 128^2 kernel's rate); force_tile 288 runs it
-// on any shape it accepts (tests, tools/r6/t288.py).
-#ifndef REED_GEMM288_ETA
-#define REED_GEMM288_ETA 1.10
-#endif
-bool reed_gemm288_preferred(int layout, int epi, const GemmArgs& a, int splits) {
-  static const bool on = getenv("REED_GEMM288") && atoi(getenv("REED_GEMM288")) != 0;
-  if (!on || !reed_gemm288_eligible(layout, epi, a, splits) || a.K < 256) return false;
-  const int ncu = reed_num_cus();
-  const long tm = cdiv(a.M, 256), tn = cdiv(a.N, 256);
-  const double c288 = (double)cdiv((long)cdiv(a.M, BM8) * (a.N / BN8), (long)ncu) * 4.5 / REED_GEMM288_ETA;
-  double best = (double)cdiv(tm * tn, (long)ncu) * 4.0 / reed_gemm256_rate();
-  if ((a.N % 256) != 0 && (a.N % 256) <= 128) {
-    const double w = (double)tm * (tn - 1) + 0.6 * tm;
-    if (w >= 2.0 * ncu) best = ceil(2.0 * w / ncu) / 2.0 * 4.0 / reed_gemm256_rate();
-  }
-  best = fmin(best, (double)cdiv((long)cdiv(a.M, 128) * cdiv(a.N, 128), 2L * ncu) * 2.0);
-  if (a.N % 144 == 0) best = fmin(best, (double)cdiv((long)cdiv(a.M, 256) * (a.N / 144), (long)ncu) * 2.25 / 0.92);
-  return c288 < best;
-}
-
+// (REED_GEMM288=1 does); force_tile 288 runs it on any shape it accepts (tests, tools/r6/t288.py).
 int reed_gemm288_launch(int epi, GemmArgs a, hipStream_t stream) {
   switch (epi) {
     case EPI_BF16: return launch288<EPI_BF16>(a, stream);

@@ -24,13 +24,11 @@
 #include <utility>
 
 #include "../../include/reed_hip.h"
-#include "gemm.h"
+#include "gemm_plan.h"
 
 #ifndef REED_FP32
 #error "gemm_f32.hip belongs to the fp32-operand build (-DREED_FP32) only"
 #endif
-
-int reed_num_cus();
 
 namespace {
 
@@ -306,22 +304,7 @@ int launch(const GemmArgs& a, int epi, int splits, hipStream_t stream) {
 
 }  // namespace
 
-// The tile-selection knobs of the 16-bit kernels: accepted and without effect here (one kernel).
-static int g_force_tile = 0, g_cu_reserve = 0, g_concurrent_comm = 0;
-extern "C" int reed_gemm_force_tile(int tile) { g_force_tile = tile; return 0; }
-extern "C" int reed_set_cu_reserve(int n) { g_cu_reserve = n > 0 ? n : 0; return 0; }
-extern "C" int reed_set_concurrent_comm(int on) { g_concurrent_comm = on ? 1 : 0; return 0; }
-int reed_num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n - g_cu_reserve > 32 ? n - g_cu_reserve : 32;
-}
-extern "C" int reed_planning_cus(void) { return reed_num_cus(); }
+// (the tile-selection knobs of the 16-bit kernels — gemm_plan.cpp — are accepted and without effect here: one kernel)
 
 // The grouped weight-gradient launch is a 16-bit MFMA kernel (gemm_tn.hip): not part of this build; the caller falls back to
 // one reed_gemm(TN) per weight (ops.wgrad_group returns False on this code).
@@ -373,13 +356,14 @@ extern "C" int reed_conv3x3_down(const void* act, const void* w, const float* bi
   return conv3x3_f32("reed_conv3x3_down", act, w, bias, out, ldc, B, Hi, Wi, C, N, 0, 1, accumulate, stream);
 }
 
-int reed_gemm_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t stream) {
-  REED_CHECK_ARG(a.M > 0 && a.N > 0 && a.K > 0, "reed_gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
-  REED_CHECK_ARG(a.ldp % 4 == 0 && a.ldq % 4 == 0 && a.N % 4 == 0, "reed_gemm(fp32): leading dims and N must be multiples of 4 elements");
-  REED_CHECK_ARG(((uintptr_t)a.P % 16) == 0 && ((uintptr_t)a.Q % 16) == 0, "reed_gemm: operands must be 16-byte aligned");
+// The shape rules of the one kernel, and its split-K arithmetic: the same as the 16-bit kernels' (units of 64), so callers that size
+// slab workspaces by it (ops.linear_wgrad, engine.py) see the same slab count from either build.
+static int plan_f32(int& layout, int epi, int M, int N, int K, int& splits, bool has_slab, int* ksplit_len) {
+  REED_CHECK_ARG(M > 0 && N > 0 && K > 0, "reed_gemm: empty problem M=%d N=%d K=%d", M, N, K);
+  REED_CHECK_ARG(N % 4 == 0, "reed_gemm(fp32): leading dims and N must be multiples of 4 elements");
   if (layout == LAY_TN_TALL || layout == LAY_TN_WIDE) layout = LAY_TN;   // tile hints of the 16-bit weight-gradient kernel
-  if (layout == LAY_TN) REED_CHECK_ARG(a.M % 4 == 0, "reed_gemm(TN, fp32): M=%d must be a multiple of 4", a.M);
-  else REED_CHECK_ARG(a.K % 4 == 0, "reed_gemm(NT/NN, fp32): K=%d must be a multiple of 4", a.K);
+  if (layout == LAY_TN) REED_CHECK_ARG(M % 4 == 0, "reed_gemm(TN, fp32): M=%d must be a multiple of 4", M);
+  else REED_CHECK_ARG(K % 4 == 0, "reed_gemm(NT/NN, fp32): K=%d must be a multiple of 4", K);
   switch (epi) {
     case EPI_BF16: case EPI_GELU: case EPI_SILU: case EPI_GATE_RES: case EPI_DGELU: case EPI_DSILU: case EPI_F32:
     case EPI_ADDF32_RB: case EPI_ATOMIC_F32: case EPI_QGELU: case EPI_RES_BF16: case EPI_LS_RES:
@@ -387,20 +371,38 @@ int reed_gemm_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t st
     default: reed_set_error("reed_gemm: unknown epilogue %d", epi); return REED_ERR_ARG;
   }
   if (splits < 1) splits = 1;
-  // K per split: the same arithmetic as the 16-bit kernels (units of 64), so callers that size slab workspaces by it
-  // (ops.linear_wgrad, engine.py) see the same slab count from either build
-  const int ksteps = cdiv(a.K, 64);
+  const int ksteps = cdiv(K, 64);
   const int per = cdiv(ksteps, splits);
   splits = cdiv(ksteps, per);
-  a.ksplit_len = per * 64;
+  *ksplit_len = per * 64;
   if (splits > 1)
-    REED_CHECK_ARG(epi == EPI_ATOMIC_F32 || (epi == EPI_F32 && a.slab_stride > 0),
-                   "reed_gemm: split-K needs the atomic or slab fp32 epilogue");
+    REED_CHECK_ARG(epi == EPI_ATOMIC_F32 || (epi == EPI_F32 && has_slab), "reed_gemm: split-K needs the atomic or slab fp32 epilogue");
+  REED_CHECK_ARG(layout == LAY_NT || layout == LAY_NN || layout == LAY_TN, "reed_gemm: unknown layout %d", layout);
+  return REED_OK;
+}
+
+// the dry run of include/reed_hip.h: one kernel, whatever the knobs say
+extern "C" int reed_gemm_plan(int layout, int epilogue, int M, int N, int K, int split_k, int flags, int, int, int, int, int, int,
+                              int* launches) {
+  int ksplit_len = 0;
+  if (epilogue == EPI_GELU_ERF) epilogue = EPI_QGELU;   // (as reed_gemm: the variant is a run-time switch of this build)
+  if (!epi_layout_ok(layout, epilogue, N, split_k) || epilogue == EPI_SWIGLU) {
+    reed_set_error("reed_gemm: epilogue %d: NT only, no split-K (17: not part of the fp32-operand build)", epilogue);
+    return -REED_ERR_ARG;
+  }
+  if (const int rc = plan_f32(layout, epilogue, M, N, K, split_k, (flags & 2) != 0, &ksplit_len)) return -rc;
+  const int v[GEMM_LAUNCH_INTS] = {GK_F32, 0, M, 0, N, split_k, ksplit_len, 0, cdiv(M, Geo<2>::BT) * cdiv(N, Geo<2>::BT)};
+  if (launches) memcpy(launches, v, sizeof(v));
+  return 1;
+}
+
+int reed_gemm_launch(int layout, int epi, GemmArgs a, int splits, hipStream_t stream) {
+  REED_CHECK_ARG(a.ldp % 4 == 0 && a.ldq % 4 == 0, "reed_gemm(fp32): leading dims and N must be multiples of 4 elements");
+  REED_CHECK_ARG(((uintptr_t)a.P % 16) == 0 && ((uintptr_t)a.Q % 16) == 0, "reed_gemm: operands must be 16-byte aligned");
+  if (const int rc = plan_f32(layout, epi, a.M, a.N, a.K, splits, a.slab_stride > 0, &a.ksplit_len)) return rc;
   switch (layout) {
     case LAY_NT: return launch<LAY_NT>(a, epi, splits, stream);
     case LAY_NN: return launch<LAY_NN>(a, epi, splits, stream);
-    case LAY_TN: return launch<LAY_TN>(a, epi, splits, stream);
   }
-  reed_set_error("reed_gemm: unknown layout %d", layout);
-  return REED_ERR_ARG;
+  return launch<LAY_TN>(a, epi, splits, stream);
 }

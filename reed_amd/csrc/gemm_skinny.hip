@@ -1,4 +1,4 @@
-// Skinny NT GEMM for gfx950: y = epilogue(x W^T) for a FEW rows of x — the tail launch of the dispatcher's ragged-M split (gemm.hip):
+// Skinny NT GEMM for gfx950: y = epilogue(x W^T) for a FEW rows of x — the tail launch of the planner's ragged-M split (gemm_plan.cpp):
 // the 64 rows that 64 x 257 ViT tokens leave beyond the last full 256-row tile (frozen towers).
 //
 // Why its own kernel (round 4, profiles/r4_tower64_kernel_stats.csv): on the 128^2 kernel those 64 rows made 4-32 workgroups that each
@@ -118,15 +118,7 @@ int launch_skinny(const GemmArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// NT, the row-free bf16 / fp32-residual epilogues of a frozen tower's forward, K a multiple of 64, N of 64, no split-K
-bool reed_gemm_skinny_eligible(int layout, int epi, const GemmArgs& a, int splits) {
-  const bool epi_ok = epi == EPI_BF16 || epi == EPI_GELU || epi == EPI_SILU || epi == EPI_QGELU || epi == EPI_GELU_ERF ||
-                      epi == EPI_GELU_G || epi == EPI_SILU_G ||
-                      epi == EPI_RES_BF16 || epi == EPI_LS_RES || epi == EPI_GATE_RES || epi == EPI_SWIGLU;
-  return layout == LAY_NT && epi_ok && splits <= 1 && a.K % SK == 0 && a.K >= SK && a.N % 64 == 0 && a.M >= 1 &&
-         (long)cdiv(a.M, 16) * (a.N / 64) < (1l << 30);
-}
-
+// (shapes: NT, an epilogue of EPIS_SKINNY, K a multiple of 64, N of 64, no split-K: gemm_plan.cpp)
 int reed_gemm_skinny_launch(int epi, GemmArgs a, hipStream_t stream) {
   switch (epi) {
     case EPI_BF16: return launch_skinny<EPI_BF16>(a, stream);

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "gemm_common.hpp"
+#include "gemm_plan.h"
 
 #if defined(REED_CLK_PROBE) || defined(REED_CLK_SEG)
 // diagnostic builds only (tools/_ab/build_variant.py clk -DREED_CLK_PROBE, tools/clk_probe_tn.py: stamps around the K loop;
@@ -27,7 +28,6 @@ extern "C" int reed_clk_probe_read_tn(unsigned long long* out, int n) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(reed_clk_buf_tn), sizeof(unsigned long long) * n);
 }
 #endif
-int reed_num_cus();   // gemm256.hip
 namespace {
 using namespace gemm_detail;
 
@@ -288,7 +288,6 @@ int launch_tn(const GemmArgs& a, int splits, hipStream_t stream) {
 
 }  // namespace
 
-int reed_num_cus();   // gemm256.hip
 int reed_gemm256w_tn_group_launch(int n, const GemmArgs* probs, hipStream_t stream, int* launched);   // gemm256w.hip
 
 // n <= 4 problems dw_i[M_i, N_i] f32 (+)= dy_i[K, M_i]^T x_i[K, N_i] (+ optional dbias_i) sharing the token count K.
@@ -335,11 +334,7 @@ int reed_gemm_tn_group_launch(int n, const GemmArgs* probs, hipStream_t stream) 
   return REED_OK;
 }
 
-// tile: 1 = 256x128, 2 = 128x256.  EPI_F32 only (weight gradients); the caller has validated the arguments.
+// tile: 1 = 256x128, 2 = 128x256 (N a multiple of 256).  EPI_F32 only (weight gradients); gemm_plan.cpp has validated the shape.
 int reed_gemm_tn_launch(int tile, GemmArgs a, int splits, hipStream_t stream) {
-  if (tile == 2) {
-    REED_CHECK_ARG(a.N % 256 == 0, "reed_gemm(TN 128x256): N=%d must be a multiple of 256", a.N);
-    return launch_tn<true>(a, splits, stream);
-  }
-  return launch_tn<false>(a, splits, stream);
+  return tile == 2 ? launch_tn<true>(a, splits, stream) : launch_tn<false>(a, splits, stream);
 }

@@ -392,7 +392,7 @@ class Engine:
             raise RuntimeError("reed_amd.SiT: model.precision changed between forward and backward")
         prev = ops.use(prec)
         # gradient buckets are reduced beside this backward's GEMMs (RCCL channels hold CUs): only then does the library keep to
-        # kernels that degrade gracefully without every CU (csrc/gemm256.hip:reed_set_concurrent_comm); the forward, the
+        # kernels that degrade gracefully without every CU (csrc/gemm_plan.cpp:reed_set_concurrent_comm); the forward, the
         # optimiser and the sampler run with no collective in flight (the step waits for the last bucket before the update)
         comm = self.reducer is not None and self.reducer.active()
         if comm:

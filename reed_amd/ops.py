@@ -4,6 +4,7 @@ PyTorch is used for device memory and streams only; every function here launches
 HIP kernels on torch's current stream and raises if the library is unavailable.
 Pointer arguments may be torch tensors or raw integer device addresses (for sub-views of arenas).
 """
+import contextlib
 import ctypes
 
 import math
@@ -200,13 +201,25 @@ def gemm_forced_tile():
 def gemm_force_tile(tile):
     """0 = heuristic; 128 / 256 (eight waves) / 257 (four 128x128 waves, one tile per workgroup) / 258 (the same, persistent
     form wherever it applies) / 144 / 64 (the skinny one-wave tiles) = force that GEMM kernel
-    where it applies; 259 = the heuristic plus the column split of csrc/gemm.hip (tests and A/B timing).  Set in both builds of the library."""
+    where it applies; 288 = the 256x288 kernel; 259 = the heuristic plus the column split (csrc/gemm_plan.cpp; tests and A/B timing).  Set in both builds of the library."""
     global _FORCED_TILE
     _FORCED_TILE = int(tile)
     for prec in ("bf16", "fp16"):
         _lib.load(prec).reed_gemm_force_tile(int(tile))
     if "fp32" in _lib.loaded():
         _lib.load("fp32").reed_gemm_force_tile(int(tile))
+
+
+@contextlib.contextmanager
+def forced_tile(tile):
+    """gemm_force_tile(tile) for the block; after it — also when the block raises — what was forced before (0, the heuristic,
+    unless blocks nest)."""
+    prev = _FORCED_TILE
+    gemm_force_tile(tile)
+    try:
+        yield
+    finally:
+        gemm_force_tile(prev)
 
 
 WGRAD_SLOTS = 512  # resident 128x128 blocks: 256 CUs x 2 (64 KiB LDS, <=128 VGPRs... see gemm.hip launch bounds)
@@ -243,7 +256,7 @@ def cu_reserve():
 
 def set_concurrent_comm(on):
     """Collectives run beside the GEMMs from now on (data-parallel training): the library keeps to kernels that degrade
-    gracefully when RCCL's channels hold CUs (csrc/gemm256.hip:reed_set_concurrent_comm)."""
+    gracefully when RCCL's channels hold CUs (csrc/gemm_plan.cpp:reed_set_concurrent_comm)."""
     for prec in ("bf16", "fp16") + (("fp32",) if "fp32" in _lib.loaded() else ()):
         _lib.load(prec).reed_set_concurrent_comm(1 if (on and _COMM_FORMS) else 0)
 
@@ -314,6 +327,29 @@ def wgrad_group_deal(shapes, cus=256, precision="bf16"):
         out.append(run)
     assert sum(len(r) for r in out) == T
     return out
+
+
+GEMM_KERNELS = ("128", "144", "288", "256x8", "256w", "256wp", "skinny", "tn_tall", "tn_wide", "f32")
+
+
+def gemm_plan(lay, epi, M, N, K, split_k=1, *, dbias=False, slab=False, dot_operands=True, rows_per_gate=1, ncu=0, forced=0,
+              colsplit=-1, use288=-1, concurrent_comm=False, precision="bf16"):
+    """Which kernels reed_gemm(lay, epi, M, N, K, split_k) launches, on which part of the output (reed_gemm_plan: host arithmetic,
+    runs without a GPU).  ncu = 0: the CUs the library plans for now; colsplit / use288 = -1: as the environment set them.
+    Returns (0, [launch, ...]) with launch = dict(kernel=GEMM_KERNELS name, row0, rows, col0, cols, splits, ksplit_len, tile_gm,
+    grid), or (reed_gemm's error code, [])."""
+    out = (ctypes.c_int * 27)()
+    n = _lib.load(precision).reed_gemm_plan(int(lay), int(epi), int(M), int(N), int(K), int(split_k),
+                                            int(bool(dbias)) | 2 * int(bool(slab)) | 4 * int(bool(dot_operands)), int(rows_per_gate),
+                                            int(ncu), int(forced), int(colsplit), int(use288), int(bool(concurrent_comm)),
+                                            ctypes.cast(out, ctypes.c_void_p))
+    if n < 0:
+        return -n, []
+    keys = ("kernel", "row0", "rows", "col0", "cols", "splits", "ksplit_len", "tile_gm", "grid")
+    launches = [dict(zip(keys, out[9 * i:9 * i + 9])) for i in range(n)]
+    for l in launches:
+        l["kernel"] = GEMM_KERNELS[l["kernel"]]
+    return 0, launches
 
 
 def wgrad_group(problems, tokens, accumulate=False):

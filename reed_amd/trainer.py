@@ -69,7 +69,7 @@ class TrainStep:
         self.grad_accum = max(1, int(grad_accum))
         self.global_step = 0
         self._micro = 0
-        # CU reserve for the GEMM grids under data parallelism (csrc/gemm256.hip:reed_num_cus): RCCL's channels hold CUs while
+        # CU reserve for the GEMM grids under data parallelism (csrc/gemm_plan.cpp:reed_num_cus): RCCL's channels hold CUs while
         # a bucket is in flight, and grids planned as exactly one round of all CUs then take two.  How many CUs RCCL takes
         # depends on its version, topology and message size, so it can be MEASURED — opt-in (no 8-GPU run has
         # validated it yet, and a measured choice makes runs differ in their kernel plans: any reserve > 0 leaves fewer than

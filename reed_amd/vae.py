@@ -27,6 +27,7 @@ GroupNorm + SiLU + conv_out to 8 channels (double_z), quant_conv (1x1, 8 -> 8), 
 operands fp32: the reference encodes in fp32 with PyTorch's default TF32 convolutions (10 mantissa bits), which `fp16` operands
 match at the 16-bit rate; `bf16` is the fastest and coarsest.
 """
+import contextlib
 import os
 import types
 
@@ -437,34 +438,31 @@ class _HipEncode(_HipVAE):
             raise ValueError("reed_vae_moments takes 8 moment channels (latent_channels = 4)")
         raw = raw.contiguous()
         B = raw.shape[0]
-        prev, tile = ops.use(precision), ops.gemm_forced_tile()
-        pin = precision != "fp32" and tile != 128
-        if pin:
-            ops.gemm_force_tile(128)
+        prev = ops.use(precision)
+        pin = precision != "fp32" and ops.gemm_forced_tile() != 128
         try:
-            x = self._image_conv(raw, precision)
-            if x.shape[-1] != e.conv_in.out_channels:
-                raise ValueError(f"precision {precision!r} needs channel counts that are multiples of 128")
-            for i, d in enumerate(e.down_blocks):
-                for j, r in enumerate(d.resnets):
-                    x = self._resnet(x, f"encoder.down_blocks.{i}.resnets.{j}", r, precision)
-                if d.downsamplers is not None:
-                    x = self._conv(x, f"encoder.down_blocks.{i}.downsamplers.0.conv", d.downsamplers[0].conv, precision, 9,
-                                   down=True)
-            m = e.mid_block
-            x = self._resnet(x, "encoder.mid_block.resnets.0", m.resnets[0], precision)
-            x = self._attention(x, "encoder.mid_block.attentions.0", m.attentions[0], precision)
-            x = self._resnet(x, "encoder.mid_block.resnets.1", m.resnets[1], precision)
-            y = self._conv(x, "encoder.conv_out", e.conv_out, precision, 9, norm=e.conv_norm_out, silu=True)
-            _, h, w, ldc = y.shape
-            q = v.quant_conv
-            out = torch.empty(B, 8, h, w, dtype=torch.float32, device=raw.device)
-            ops.vae_moments(y, ldc, B, h, w, q.weight.detach().float().reshape(8, 8).contiguous(),
-                            q.bias.detach().float().contiguous(), out)
-            return out
+            with ops.forced_tile(128) if pin else contextlib.nullcontext():
+                x = self._image_conv(raw, precision)
+                if x.shape[-1] != e.conv_in.out_channels:
+                    raise ValueError(f"precision {precision!r} needs channel counts that are multiples of 128")
+                for i, d in enumerate(e.down_blocks):
+                    for j, r in enumerate(d.resnets):
+                        x = self._resnet(x, f"encoder.down_blocks.{i}.resnets.{j}", r, precision)
+                    if d.downsamplers is not None:
+                        x = self._conv(x, f"encoder.down_blocks.{i}.downsamplers.0.conv", d.downsamplers[0].conv, precision, 9,
+                                       down=True)
+                m = e.mid_block
+                x = self._resnet(x, "encoder.mid_block.resnets.0", m.resnets[0], precision)
+                x = self._attention(x, "encoder.mid_block.attentions.0", m.attentions[0], precision)
+                x = self._resnet(x, "encoder.mid_block.resnets.1", m.resnets[1], precision)
+                y = self._conv(x, "encoder.conv_out", e.conv_out, precision, 9, norm=e.conv_norm_out, silu=True)
+                _, h, w, ldc = y.shape
+                q = v.quant_conv
+                out = torch.empty(B, 8, h, w, dtype=torch.float32, device=raw.device)
+                ops.vae_moments(y, ldc, B, h, w, q.weight.detach().float().reshape(8, 8).contiguous(),
+                                q.bias.detach().float().contiguous(), out)
+                return out
         finally:
-            if pin:
-                ops.gemm_force_tile(tile)
             ops.use(prev)
 
 

@@ -138,36 +138,35 @@ def test_delta_from_the_dgrad_epilogue(dev, prec, b, H, hd, force, T):
     w = (torch.randn(D, D, generator=g) / D ** 0.5).to(hdt).to(dev)
     qkv = torch.randn(b, T, 3, H, hd, generator=g).to(hdt).to(dev)
     prev = ops.use(prec)
-    ops.gemm_force_tile(force)
     try:
-        o = torch.zeros(b, T, D, dtype=hdt, device=dev)
-        lse = torch.zeros(b, H, T, device=dev)
-        ops.attention_fwd(qkv, o, lse, b, T, H, hd)
-        do0 = torch.empty(M, D, dtype=hdt, device=dev)
-        ops.gemm(ops.NN, ops.EPI_BF16, dy, w, M, D, D, do0, D, D, D)
-        S = 1 if hd == 64 else 2
-        runs = []
-        for _ in range(2):
-            do1 = torch.full((M, D), float("nan"), dtype=hdt, device=dev)
-            dpart = torch.full((H, S, M), float("nan"), device=dev)
-            if not ops.dgrad_with_head_dots(dy, w, do1, o, dpart, M, D, D, hd):
-                pytest.skip("this shape's GEMM kernel has no head-dot epilogue")
-            dq = torch.full_like(qkv, float("nan"))
-            ws = torch.full((ops.attention_bwd_ws_floats(b, T, H),), float("nan"), device=dev)
-            ops.attention_bwd_dp(qkv, do1, lse, dpart, dq, ws, b, T, H, hd)
-            torch.cuda.synchronize()
-            runs.append((do1, dpart, dq))
-        do1, dpart, dq = runs[0]
-        assert all(torch.equal(x, y) for x, y in zip(runs[0], runs[1]))
-        assert torch.equal(do1, do0) and torch.isfinite(dpart).all()
-        want = (do0.double() * o.view(M, D).double()).view(M, H, hd).sum(-1)
-        torch.testing.assert_close(dpart.sum(1).T.double(), want, rtol=2e-5, atol=2e-5 * float(want.abs().max()))
-        dq0 = torch.full_like(qkv, float("nan"))
-        ops.attention_bwd(qkv, o, do0, lse, dq0, b, T, H, hd, ws=torch.empty_like(ws))
-        a, r = dq.float(), dq0.float()
-        assert torch.isfinite(a).all() and (a - r).abs().max().item() <= 1e-2 * r.abs().max().item()
+        with ops.forced_tile(force):
+            o = torch.zeros(b, T, D, dtype=hdt, device=dev)
+            lse = torch.zeros(b, H, T, device=dev)
+            ops.attention_fwd(qkv, o, lse, b, T, H, hd)
+            do0 = torch.empty(M, D, dtype=hdt, device=dev)
+            ops.gemm(ops.NN, ops.EPI_BF16, dy, w, M, D, D, do0, D, D, D)
+            S = 1 if hd == 64 else 2
+            runs = []
+            for _ in range(2):
+                do1 = torch.full((M, D), float("nan"), dtype=hdt, device=dev)
+                dpart = torch.full((H, S, M), float("nan"), device=dev)
+                if not ops.dgrad_with_head_dots(dy, w, do1, o, dpart, M, D, D, hd):
+                    pytest.skip("this shape's GEMM kernel has no head-dot epilogue")
+                dq = torch.full_like(qkv, float("nan"))
+                ws = torch.full((ops.attention_bwd_ws_floats(b, T, H),), float("nan"), device=dev)
+                ops.attention_bwd_dp(qkv, do1, lse, dpart, dq, ws, b, T, H, hd)
+                torch.cuda.synchronize()
+                runs.append((do1, dpart, dq))
+            do1, dpart, dq = runs[0]
+            assert all(torch.equal(x, y) for x, y in zip(runs[0], runs[1]))
+            assert torch.equal(do1, do0) and torch.isfinite(dpart).all()
+            want = (do0.double() * o.view(M, D).double()).view(M, H, hd).sum(-1)
+            torch.testing.assert_close(dpart.sum(1).T.double(), want, rtol=2e-5, atol=2e-5 * float(want.abs().max()))
+            dq0 = torch.full_like(qkv, float("nan"))
+            ops.attention_bwd(qkv, o, do0, lse, dq0, b, T, H, hd, ws=torch.empty_like(ws))
+            a, r = dq.float(), dq0.float()
+            assert torch.isfinite(a).all() and (a - r).abs().max().item() <= 1e-2 * r.abs().max().item()
     finally:
-        ops.gemm_force_tile(0)
         ops.use(prev)
 
 

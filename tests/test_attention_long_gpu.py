@@ -96,8 +96,7 @@ def test_attention_bwd_long_delta_from_the_dgrad_epilogue(dev, prec, b, H, hd, f
     dy = (torch.randn(M, D, generator=g) * 0.5).to(hdt).to(dev)
     w = (torch.randn(D, D, generator=g) / D ** 0.5).to(hdt).to(dev)
     qkv = torch.randn(b, T, 3, H, hd, generator=g).to(hdt).to(dev)
-    ops.gemm_force_tile(force)
-    try:
+    with ops.forced_tile(force):
         o = torch.zeros(b, T, D, dtype=hdt, device=dev)
         lse = torch.zeros(b, H, T, device=dev)
         ops.attention_fwd(qkv, o, lse, b, T, H, hd)
@@ -120,8 +119,6 @@ def test_attention_bwd_long_delta_from_the_dgrad_epilogue(dev, prec, b, H, hd, f
         ops.attention_bwd(qkv, o, do0, lse, dq0, b, T, H, hd, ws=torch.empty_like(ws))
         a, r = dq.float(), dq0.float()
         assert torch.isfinite(a).all() and (a - r).abs().max().item() <= 1e-2 * r.abs().max().item()
-    finally:
-        ops.gemm_force_tile(0)
 
 
 def test_attention_bwd_long_refusals(dev):

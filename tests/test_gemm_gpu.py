@@ -278,17 +278,16 @@ def test_wgrad_group_beside_a_collective_is_the_two_workgroup_kernel(dev):
         probs.append((dy, x, out[:n_out * k_in].view(n_out, k_in), out[n_out * k_in:], n_out, k_in))
 
     def run(tile, comm):
-        ops.gemm_force_tile(tile)
         ops.set_concurrent_comm(comm)
         try:
-            for q in probs:
-                q[2].fill_(float("nan"))
-                q[3].fill_(float("nan"))
-            assert ops.wgrad_group(probs, tokens)
-            return [(q[2].clone(), q[3].clone()) for q in probs]
+            with ops.forced_tile(tile):
+                for q in probs:
+                    q[2].fill_(float("nan"))
+                    q[3].fill_(float("nan"))
+                assert ops.wgrad_group(probs, tokens)
+                return [(q[2].clone(), q[3].clone()) for q in probs]
         finally:
             ops.set_concurrent_comm(False)
-            ops.gemm_force_tile(0)
 
     two = run(128, False)
     beside = run(0, True)
@@ -316,16 +315,13 @@ def test_wgrad_group_items_bit_identical_to_the_two_workgroup_kernel(dev, tokens
         probs.append((dy, x, out[:n_out * k_in].view(n_out, k_in), out[n_out * k_in:] if has_b else None, n_out, k_in))
 
     def run(tile, acc):
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             for q in probs:
                 q[2].fill_(0.25 if acc else float("nan"))
                 if q[3] is not None:
                     q[3].fill_(-0.5 if acc else float("nan"))
             assert ops.wgrad_group(probs, tokens, accumulate=acc)
             return [(q[2].clone(), None if q[3] is None else q[3].clone()) for q in probs]
-        finally:
-            ops.gemm_force_tile(0)
 
     for acc in (False, True):
         ref, got = run(128, acc), run(0, acc)
@@ -562,7 +558,7 @@ def test_persistent_form_with_cu_reserve(dev, force_tile, reserve):
 @pytest.mark.parametrize("N,K", [(1024, 1024), (4096, 1024), (1024, 4096)])
 def test_ragged_m_split_is_bit_invisible(dev, N, K, force_tile):
     """M = 64 x 257 (a ViT tower at batch 64): the dispatcher sends the 64 full tile rows and the 64 tail rows out as two
-    launches where the ragged 65th row tile would cost a whole round of the chip (csrc/gemm.hip: ragged-M split) — outputs
+    launches where the ragged 65th row tile would cost a whole round of the chip (csrc/gemm_plan.cpp: ragged-M split) — outputs
     bit-identical to the one-launch form of a forced tile, for the plain, QuickGELU, GELU(erf), bf16-residual and LayerScale
     epilogues, and nothing written past row M - 1."""
     if force_tile != 0:
@@ -578,8 +574,7 @@ def test_ragged_m_split_is_bit_invisible(dev, N, K, force_tile):
     gamma = torch.randn(N, generator=g).to(dev)
 
     def run(tile):
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             o_plain = torch.full((M + 1, N), float("nan"), dtype=torch.bfloat16, device=dev)
             ops.gemm(ops.NT, ops.EPI_BF16, x, w, M, N, K, o_plain, K, K, N, bias=b)
             o_q = torch.full((M + 1, N), float("nan"), dtype=torch.bfloat16, device=dev)
@@ -592,8 +587,6 @@ def test_ragged_m_split_is_bit_invisible(dev, N, K, force_tile):
             ops.gemm(ops.NT, ops.EPI_LS_RES, x, w, M, N, K, o_l, K, K, N, R=r32, ldr=N, bias=b, gate=gamma)
             torch.cuda.synchronize()
             return o_plain, o_q, o_e, o_r, o_l
-        finally:
-            ops.gemm_force_tile(0)
 
     split, whole = run(0), run(256)
     for name, a, c in zip(("plain", "quickgelu", "gelu_erf", "res_bf16", "ls_res"), split, whole):
@@ -650,7 +643,7 @@ def test_column_split_is_bit_identical_to_one_launch(dev, case):
     """Round 6 (a switch, off by default: force_tile 259 / REED_GEMM_COLSPLIT=1 — measured equal in the b = 32 step): where a leading
     block of tile columns fills whole rounds of the chip exactly (8192 tokens x 4608 columns = 2.25 rounds of 256^2 tiles: 16 of the
     18 tile columns are two rounds) reed_gemm sends that block to the four-wave 256^2 kernel and the remaining columns out as a
-    second launch on offset pointers (csrc/gemm.hip).  Every epilogue operand with a column index moves
+    second launch on offset pointers (csrc/gemm_plan.cpp plans it, csrc/gemm.hip offsets the pointers).  Every epilogue operand with a column index moves
     with it — Q, C, C2, R, bias, gate — and every element is formed by the same products in the same order: the same bits as the
     single launch on 256x144 tiles (force_tile 144) and on 256^2 tiles (257)."""
     from reed_amd import ops
@@ -667,8 +660,7 @@ def test_column_split_is_bit_identical_to_one_launch(dev, case):
     xin = torch.randn(M, Hm, generator=g).to(dev)
     outs = []
     for tile in (259, 144, 257):
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             c = torch.full((M, Hm), float("nan"), dtype=torch.bfloat16, device=dev)
             c2 = torch.full((M, Hm), float("nan"), dtype=torch.bfloat16, device=dev)
             if case in ("fc1_fwd_gelu", "fc1_fwd_gelu_g"):
@@ -690,8 +682,6 @@ def test_column_split_is_bit_identical_to_one_launch(dev, case):
             else:
                 ops.gemm(ops.NT, ops.EPI_BF16, x, w, M, Hm, K, c, K, K, Hm, bias=bias)
                 outs.append((c,))
-        finally:
-            ops.gemm_force_tile(0)
     torch.cuda.synchronize()
     for o in outs[1:]:
         for a, b in zip(outs[0], o):
@@ -718,8 +708,7 @@ def test_tile288(dev, M, N, K, epi, force_tile):
     r = _bf(torch.randn(M, N, generator=g)).to(dev)
 
     def run(tile):
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             c = torch.full((M + 1, N), float("nan"), dtype=torch.bfloat16, device=dev)
             c2 = torch.full((M + 1, N), float("nan"), dtype=torch.bfloat16, device=dev)
             if epi == "plain":
@@ -730,8 +719,6 @@ def test_tile288(dev, M, N, K, epi, force_tile):
                 return (c, c2)
             ops.gemm(ops.NT, ops.EPI_DGELU if epi == "dgelu" else ops.EPI_MUL, x, w, M, N, K, c, K, K, N, R=r, ldr=N)
             return (c,)
-        finally:
-            ops.gemm_force_tile(0)
 
     o288, o144 = run(288), run(144)
     torch.cuda.synchronize()
@@ -754,9 +741,6 @@ def test_tile288_identity(dev, force_tile):
     x = torch.eye(M, K, device=dev).to(torch.bfloat16)
     w = (torch.arange(N * K, device=dev).reshape(N, K) % 251).float().to(torch.bfloat16)
     out = torch.zeros(M, N, dtype=torch.bfloat16, device=dev)
-    ops.gemm_force_tile(288)
-    try:
+    with ops.forced_tile(288):
         ops.gemm(ops.NT, ops.EPI_BF16, x, w, M, N, K, out, K, K, N)
-    finally:
-        ops.gemm_force_tile(0)
     assert torch.equal(out.float(), w.float().t().contiguous())

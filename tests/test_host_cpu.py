@@ -700,3 +700,30 @@ def test_wgrad_group_deal_covers_every_gradient_element_once(shapes):
     # a CU reserve (collectives holding CUs) leaves too few CUs for one round: the form does not apply
     assert ops.wgrad_group_deal([(1152, 4608, 1), (4608, 1152, 1), (1152, 1152, 1), (3456, 1152, 1)], 224) is None
     assert ops.wgrad_group_deal([(384, 1536, 1), (1536, 384, 1), (384, 384, 1), (1152, 384, 1)], 256) is None    # SiT-S/2: too thin
+
+
+def test_gemm_plan_selects_what_the_recorded_dispatcher_launched():
+    """Which kernels a reed_gemm call runs, on which rows and columns, with which grid, split and tile walk: ops.gemm_plan
+    (csrc/gemm_plan.cpp, host arithmetic) against what the dispatcher launched before the planner existed, recorded call by call
+    (tests/golden/gemm_plan.npz, tools/gen_golden.py:g_gemm_plan) — SiT-S .. XL and ViT-B .. g widths at b = 8 .. 256, the ragged
+    tower token counts, every layout, epilogue value, forced tile, 256 / 240 / 232 CUs, beside a collective or not, and the four
+    settings of the column-split and 256x288 switches.  Every field of every row, refusals (1001 / 1002) included."""
+    from reed_amd import ops
+    g = np.load(os.path.join(ROOT, "tests", "golden", "gemm_plan.npz"))
+    t = np.stack([g[f"c{j:02d}"].astype(np.int64) for j in range(42)], axis=1)
+    assert len(t) > 150000 and set(np.unique(t[:, 9])) == {0, 64, 128, 144, 256, 257, 258, 259, 288} and set(np.unique(t[:, 1])) >= set(range(18))
+    kernels = {name: i for i, name in enumerate(ops.GEMM_KERNELS)}
+    keys = ("row0", "rows", "col0", "cols", "splits", "ksplit_len", "tile_gm", "grid")
+    got = np.zeros((len(t), 29), dtype=np.int64)
+    for i, (lay, epi, M, N, K, splits, flags, rpg, ncu, forced, colsplit, use288, comm) in enumerate(t[:, :13].tolist()):
+        rc, launches = ops.gemm_plan(lay, epi, M, N, K, splits, dbias=flags & 1, slab=flags & 2, dot_operands=flags & 4, rows_per_gate=rpg,
+                                     ncu=ncu, forced=forced, colsplit=colsplit, use288=use288, concurrent_comm=comm)
+        got[i, 0], got[i, 1] = rc, len(launches)
+        for j, l in enumerate(launches):
+            got[i, 2 + 9 * j:11 + 9 * j] = [kernels[l["kernel"]]] + [l[k] for k in keys]
+    bad = np.nonzero((got != t[:, 13:]).any(axis=1))[0]
+    assert len(bad) == 0, (len(bad), [(t[i, :13].tolist(), t[i, 13:].tolist(), got[i].tolist()) for i in bad[:5]])
+    # the fp32-operand build has one kernel, whatever the knobs say
+    rc, launches = ops.gemm_plan(0, 0, 8192, 1152, 1152, forced=144, precision="fp32")
+    assert rc == 0 and [l["kernel"] for l in launches] == ["f32"] and (launches[0]["rows"], launches[0]["cols"]) == (8192, 1152)
+    assert ops.gemm_plan(0, 17, 8192, 8192, 1536, precision="fp32")[0] == 1001 and ops.gemm_plan(0, 0, 8192, 1150, 1152)[0] == 1001

@@ -522,14 +522,13 @@ def test_fp16_library_gemm_and_attention(dev):
     prev = ops.use("fp16")
     try:
         for tile in (256, 257, 258, 144):
-            ops.gemm_force_tile(tile)
-            o1 = torch.full((M, N), float("nan"), dtype=torch.float16, device=dev)
-            o2 = torch.full((M, N), float("nan"), dtype=torch.float16, device=dev)
-            ops.linear_fwd(x, w, None, o1)
-            ops.gemm(ops.NN, ops.EPI_BF16, x, wn, M, N, K, o2, K, N, N)
-            outs[tile] = (o1, o2)
+            with ops.forced_tile(tile):
+                o1 = torch.full((M, N), float("nan"), dtype=torch.float16, device=dev)
+                o2 = torch.full((M, N), float("nan"), dtype=torch.float16, device=dev)
+                ops.linear_fwd(x, w, None, o1)
+                ops.gemm(ops.NN, ops.EPI_BF16, x, wn, M, N, K, o2, K, N, N)
+                outs[tile] = (o1, o2)
     finally:
-        ops.gemm_force_tile(0)
         ops.use(prev)
     torch.testing.assert_close(outs[257][0].float(), x.float() @ w.float().t(), atol=4e-3, rtol=2e-3)
     torch.testing.assert_close(outs[257][1].float(), x.float() @ wn.float(), atol=4e-3, rtol=2e-3)

@@ -577,8 +577,7 @@ def test_tile_choice_is_bit_invisible_at_small_local_batch(dev):
     lf = SILoss(enc_names=["dinov2-vit-l"], loss_weights={"dinov2-vit-l": 1.0})
 
     def step(tile):
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             for p in m.parameters():
                 p.grad = None
             m.engine().zero_grad()
@@ -587,8 +586,6 @@ def test_tile_choice_is_bit_invisible_at_small_local_batch(dev):
             loss.backward()
             torch.cuda.synchronize()
             return float(loss.detach()), m._arena.grad.clone()
-        finally:
-            ops.gemm_force_tile(0)
 
     l0, g0 = step(0)
     l1, g1 = step(128)
@@ -635,8 +632,7 @@ def test_bench_plan_matches_the_golden_pinned_plan_at_b256(dev, monkeypatch):
     def step(tile, dp, group):
         m.engine().fused_delta = dp != "0"
         monkeypatch.setenv("REED_WGRAD_GROUP", group)
-        ops.gemm_force_tile(tile)
-        try:
+        with ops.forced_tile(tile):
             for p in m.parameters():
                 p.grad = None
             m.engine().zero_grad()
@@ -646,8 +642,6 @@ def test_bench_plan_matches_the_golden_pinned_plan_at_b256(dev, monkeypatch):
             loss.backward()
             torch.cuda.synchronize()
             return float(loss.detach()), m._arena.grad.clone()
-        finally:
-            ops.gemm_force_tile(0)
 
     L = m._layout
 

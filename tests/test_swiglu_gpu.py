@@ -42,12 +42,9 @@ def _run(c, M, Hd, K, bias, tile=0, out=None):
     from reed_amd import ops
     if out is None:
         out = torch.full((M, Hd), NAN, dtype=torch.bfloat16, device=c["x"].device)
-    ops.gemm_force_tile(tile)
-    try:
+    with ops.forced_tile(tile):
         ops.gemm(ops.NT, ops.EPI_SWIGLU, c["x"], c["pw"], M, 2 * Hd, K, out, K, K, out.stride(0), bias=c["pb"] if bias else None)
         torch.cuda.synchronize()
-    finally:
-        ops.gemm_force_tile(0)
     return out
 
 

@@ -915,6 +915,108 @@ def g_init(ref_sit, ref_loss, ref_samplers):
     save("init", **out)
 
 
+# ---- GEMM kernel selection (tests/golden/gemm_plan.npz) --------------------------------------------------------------------
+# What reed_gemm launched for a grid of calls BEFORE csrc/gemm_plan.cpp existed: run at commit ccf565e (the parent of the planner)
+# on a recording build of that commit's library — every leaf launcher (the 128^2 launch, reed_gemm144_launch, reed_gemm288_launch,
+# reed_gemm256_launch, both forms of launch256w, reed_gemm_skinny_launch, reed_gemm_tn_launch) noted {kernel, M, N, K, P, Q, grid,
+# ksplit_len, tile_gm} and returned without launching; `reed_rec_take(long out[8 * 11])` handed the notes over.  Without a GPU the
+# library plans for 256 CUs (the MI355X's count); reed_set_cu_reserve gives the others.  tests/test_host_cpu.py demands that
+# ops.gemm_plan returns every row.  Columns of `inp`: layout, epilogue, M, N, K, splits, flags (1 = bias gradient given, 2 = slab
+# stride given, 4 = R and C2 given), rows_per_gate, ncu, forced tile, column split, 256x288 switch, concurrent comm; of `out`:
+# status, launches, then 3 x {kernel, row0, rows, col0, cols, splits, ksplit_len, tile_gm, grid}.
+GEMM_PLAN_KERNELS = ("128", "144", "288", "256x8", "256w", "256wp", "skinny", "tn_tall", "tn_wide")   # the recorder's numbering
+GEMM_PLAN_EPIS = tuple(range(18)) + (18, 99)     # every EPI_* value (0 .. 17) and two that are none
+GEMM_PLAN_FORCED = (0, 64, 128, 144, 256, 257, 258, 259, 288)
+
+
+def gemm_plan_grid(colsplit, g288):
+    """The rows of one (REED_GEMM_COLSPLIT, REED_GEMM288) setting, as tuples in `inp`'s column order."""
+    Ms = [b * 256 for b in (8, 16, 32, 48, 64, 128, 256)] + [64 * 257, 64 * 261, 64, 2112]     # (1024 x 8 / 32 are among the first)
+    edge = [4352, 6400, 20224, 26368]    # beside a boundary of the ragged-tile weights 0.6 / RAG_COST at 232 / 240 / 256 CUs
+    widths = []
+    for D in (384, 768, 1024, 1152, 1280, 1536):          # SiT-S/B/L/XL, ViT-B/L/H/g: qkv, proj, fc1, fc2
+        widths += [(3 * D, D), (D, D), (4 * D, D), (D, 4 * D)]
+    widths += [(8192, 1536), (1536, 4096),                 # ViT-g's SwiGLU w12 (packed) and w3
+               (2048, 1152), (2048, 2048), (768, 2048),    # the projector MLP
+               (720, 768), (1152, 64), (1152, 128), (1152, 192)]
+    Ms_thin = [4096, 8192, 16384, 64 * 257, 2112]
+    widths_thin = [(3456, 1152), (1152, 1152), (4608, 1152), (1152, 4608), (4096, 1024), (8192, 1536), (720, 768), (1152, 128)]
+
+    def rows(Ms, widths, ncu, forced, comm, split_list=(1,)):
+        for M in Ms:
+            for N, K in widths:
+                for lay in range(5):
+                    for epi in GEMM_PLAN_EPIS:
+                        for splits in split_list:
+                            # TN: dw [n_out, k_in] over the tokens; with and without the fused bias gradient
+                            m, n, k = (N, K, M) if lay >= 2 else (M, N, K)
+                            for db in ((0, 1) if lay == 2 else (0,)):
+                                flags = db | (2 if splits > 1 and epi == 6 else 0) | 4
+                                yield (lay, epi, m, n, k, splits, flags, 64 if epi == 13 else 256, ncu, forced, colsplit, g288, comm)
+
+    if not colsplit and not g288:
+        yield from rows(Ms, widths, 256, 0, 0, (1, 4))
+        yield from rows(edge, widths_thin, 256, 0, 0)
+        for ncu, comm in ((256, 1), (240, 0), (240, 1), (232, 0), (232, 1)):
+            yield from rows(Ms_thin + edge, widths_thin, ncu, 0, comm)
+        for forced in GEMM_PLAN_FORCED[1:]:
+            yield from rows(Ms_thin, widths_thin, 256, forced, 0)
+    else:
+        yield from rows(Ms_thin, widths_thin, 256, 0, 0)
+
+
+def _gemm_plan_record(lib_path, colsplit, g288, out_path):
+    """Child process (the two switches are read once, at load): drive reed_gemm with fake 16-byte-aligned pointers."""
+    import ctypes
+    L = ctypes.CDLL(lib_path)
+    i64, vp = ctypes.c_int64, ctypes.c_void_p
+    L.reed_gemm.argtypes = [ctypes.c_int, ctypes.c_int, vp, i64, vp, i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, i64, vp, i64, vp,
+                            i64, vp, vp, i64, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, i64, vp]
+    P, Q, C, C2, R, BIAS, GATE, DB = (0x10000000 * (i + 1) for i in range(8))
+    rec = (ctypes.c_long * 88)()
+    grid = list(gemm_plan_grid(colsplit, g288))
+    inp = np.array(grid, dtype=np.int32)
+    out = np.zeros((len(grid), 29), dtype=np.int32)
+    state = None
+    for i, (lay, epi, M, N, K, splits, flags, rpg, ncu, forced, _, _, comm) in enumerate(grid):
+        if state != (ncu, forced, comm):
+            L.reed_set_cu_reserve(256 - ncu)
+            L.reed_gemm_force_tile(forced)
+            L.reed_set_concurrent_comm(comm)
+            state = (ncu, forced, comm)
+        ldp, ldq = (K, K) if lay == 0 else (K, N) if lay == 1 else (M, N)
+        rc = L.reed_gemm(lay, epi, P, ldp, Q, ldq, M, N, K, C, N, C2, N, R, N, BIAS, GATE, N, rpg, DB if flags & 1 else None, 0, splits,
+                         M * N + M if flags & 2 else 0, None)
+        n = L.reed_rec_take(rec)
+        assert n <= 3
+        out[i, 0], out[i, 1] = rc, n
+        for j in range(n):
+            kern, m, nn, k, p, q, c, gy, ksplit, gm, gx = rec[11 * j:11 * j + 11]
+            assert k == K
+            row0 = (p - P) // 2 // ldp if lay < 2 else 0
+            col0 = ((q - Q) // 2 // ldq if lay == 0 else (q - Q) // 2) if lay < 2 else 0
+            assert (p - P) == 2 * row0 * ldp and c - C in (2 * (row0 * N + col0), 4 * (row0 * N + col0)), (grid[i], rec[:11 * n])
+            out[i, 2 + 9 * j:11 + 9 * j] = (kern, row0, m, col0, nn, gy, ksplit, gm if kern in (3, 4, 5) else 0, gx)
+    np.save(out_path, np.concatenate([inp, out], axis=1))
+
+
+def g_gemm_plan(lib_path):
+    import subprocess
+    parts = []
+    with tempfile.TemporaryDirectory() as d:
+        for colsplit in (0, 1):
+            for g288 in (0, 1):
+                f = os.path.join(d, f"p{colsplit}{g288}.npy")
+                env = dict(os.environ, REED_GEMM_COLSPLIT=str(colsplit), REED_GEMM288=str(g288))
+                subprocess.run([sys.executable, "-c", f"import sys; sys.path.insert(0, {os.path.dirname(os.path.abspath(__file__))!r}); "
+                                f"import gen_golden as g; g._gemm_plan_record({lib_path!r}, {colsplit}, {g288}, {f!r})"], env=env, check=True)
+                parts.append(np.load(f))
+    t = np.concatenate(parts)
+    t = t[np.lexsort(t[:, :13].T[::-1])]      # sorted rows compress best; the columns are stored one by one for the same reason
+    narrow = lambda c: c.astype(np.int16) if np.abs(c).max() < 2 ** 15 else c
+    save("gemm_plan", **{f"c{j:02d}": narrow(t[:, j]) for j in range(t.shape[1])})
+
+
 ALL = {"init": g_init, "static": g_static, "tiny": g_tiny, "tiny512": g_tiny512, "loss_units": g_loss_units, "samplers": g_samplers, "optim_toy": g_sched,
        "s2_c1": g_s2, "b2_align": g_b2, "xl2_c2": g_xl, "xl2_c2_gnorms": g_xl_gnorms, "xl2_c4": g_xl_c4, "xl2_infer": g_xl_infer, "samplers_long": g_samplers_long, "samplers_long_xl": g_samplers_long_xl, "fp16": g_fp16, "clip": g_clip, "dataset": g_dataset, "towers": g_towers, "dinov2": g_dinov2,
        "dinov2_512": g_dinov2_512, "dinov2_g": g_dinov2_g}
@@ -923,7 +1025,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", nargs="*", default=None)
     ap.add_argument("--skip-xl", action="store_true")
+    ap.add_argument("--gemm-plan-lib", default=None, help="recording build of the library: writes gemm_plan.npz and nothing else")
     a = ap.parse_args()
+    if a.gemm_plan_lib:
+        g_gemm_plan(os.path.abspath(a.gemm_plan_lib))
+        sys.exit(0)
     torch.set_num_threads(8)
     mods = import_reference()
     for name, fn in ALL.items():
