@@ -85,6 +85,13 @@ int reed_set_concurrent_comm(int on);
  * (256x256, eight waves) / 257 (256x256, four waves, one tile per workgroup) / 258 (the same, persistent wherever that form
  * applies) / 288 (256x288) = that kernel wherever the shape allows, the heuristic elsewhere; 259 = heuristic plus the column split */
 int reed_gemm_force_tile(int tile);
+/* fp32-operand library only: how reed_gemm, reed_conv3x3 and reed_conv3x3_down multiply.  0 (the default) = exact fp32 products on
+ * v_mfma_f32_32x32x2_f32; 1 = the reference's --allow-tf32 / generate.py --tf32 on hardware without an xf32 instruction: every fp32
+ * operand element x is split into hi = bf16(x) and lo = bf16(x - hi), and a*b is taken as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi on the
+ * bf16 MFMA with fp32 accumulation: fp32 operands in memory, fp32's exponent range, an error of at most 3 * 2^-16 of |a||b| per
+ * product (TF32 rounding: 2 * 2^-11).  Same shapes, epilogues and arguments either way; the fp32 attention stays exact.  Process-wide;
+ * returns 0.  The 16-bit libraries accept 0 and answer 1 with 1002: their operands are 16-bit already. */
+int reed_gemm_f32_split(int on);
 /* Dry run of reed_gemm's kernel selection (host arithmetic, no device call, no pointers: csrc/gemm_plan.cpp).  layout, epilogue,
  * M, N, K, split_k and rows_per_gate as for reed_gemm; flags: 1 = dbias given, 2 = slab_stride > 0, 4 = R and C2 given.  The knobs
  * are explicit: ncu = CUs to plan for (<= 0: reed_planning_cus()), forced_tile as for reed_gemm_force_tile, colsplit / use288 = the
@@ -92,7 +99,8 @@ int reed_gemm_force_tile(int tile);
  * reed_set_concurrent_comm.  Returns the number of launches n <= 3 and fills launches[9 n] (NULL: count only) with, per launch,
  * {kernel, row0, rows, col0, cols, splits, ksplit_len, tile_gm, grid}: kernel 0 = 128x128 tiles, 1 = 256x144, 2 = 256x288, 3 = 256x256
  * eight waves, 4 = 256x256 four waves one-shot, 5 = the same persistent, 6 = skinny, 7 = TN 256x128, 8 = TN 128x256, 9 = the
- * fp32-operand library's one kernel; the launch computes rows [row0, row0 + rows) x columns [col0, col0 + cols) of the output with
+ * fp32-operand library's exact kernel, 10 = its split kernel (that library reports 10 while reed_gemm_f32_split(1) holds, 9
+ * otherwise, with the same grid of 128x128 tiles); the launch computes rows [row0, row0 + rows) x columns [col0, col0 + cols) of the output with
  * grid.x = grid, grid.y = splits.  Where reed_gemm would refuse the shape: minus its error code (-1001 / -1002). */
 int reed_gemm_plan(int layout, int epilogue, int M, int N, int K, int split_k, int flags, int rows_per_gate, int ncu,
                    int forced_tile, int colsplit, int use288, int concurrent_comm, int* launches);

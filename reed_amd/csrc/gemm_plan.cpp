@@ -18,6 +18,23 @@ static int g_force_tile = 0;
 extern "C" int reed_gemm_force_tile(int tile) { g_force_tile = tile; return 0; }
 int reed_gemm_forced_tile() { return g_force_tile; }
 
+// fp32-operand build: 0 = exact fp32 products (v_mfma_f32_32x32x2_f32, the default), 1 = each fp32 product as three bf16 MFMA
+// products (csrc/gemm_f32.hip: the reference's --allow-tf32).  The 16-bit builds have nothing to switch.
+static int g_f32_split = 0;
+extern "C" int reed_gemm_f32_split(int on) {
+#if defined(REED_FP32)
+  g_f32_split = on ? 1 : 0;
+  return REED_OK;
+#else
+  if (on) {
+    reed_set_error("reed_gemm_f32_split: this library's operands are 16-bit already (the mode belongs to the fp32-operand build)");
+    return REED_ERR_UNSUPPORTED;
+  }
+  return REED_OK;
+#endif
+}
+int reed_gemm_f32_split_on() { return g_f32_split; }
+
 // CUs the tile heuristics plan for = the device's count minus a reserve (reed_set_cu_reserve).  While a
 // gradient bucket is in flight RCCL's channels hold CUs, and a grid planned as exactly one round of the 256 CUs — the 256x144
 // tile at b = 32 per GPU, the grouped weight gradients' 512 slots — turns into two rounds on what is left.  The data-parallel

@@ -14,7 +14,8 @@ enum GemmKernel {
   GK_SKINNY = 6,  // gemm_skinny.hip: 16 x 64 tiles, one wave each
   GK_TN_TALL = 7, // gemm_tn.hip: 256x128 tiles
   GK_TN_WIDE = 8, // gemm_tn.hip: 128x256 tiles
-  GK_F32 = 9      // gemm_f32.hip: the fp32-operand build's one kernel
+  GK_F32 = 9,     // gemm_f32.hip: the fp32-operand build's exact kernel (fp32 MFMA)
+  GK_F32_SPLIT = 10   // gemm_f32.hip: the same build under reed_gemm_f32_split(1): three bf16 MFMA products per fp32 product
 };
 
 // What the selection reads of a call.  No pointers: only whether the optional ones were given.
@@ -53,9 +54,10 @@ int reed_gemm_plan_shape(const GemmShape& s, const GemmKnobs& k, GemmPlan* plan)
 // it looks at leading dimensions and alignment; reed_gemm_plan_shape begins with them too.
 int reed_gemm_check_dims(const GemmShape& s);
 
-// The knobs the process has set (reed_gemm_force_tile, reed_set_cu_reserve, reed_set_concurrent_comm, REED_GEMM_COLSPLIT,
-// REED_GEMM288) — their one definition, in every build of the library.
+// The knobs the process has set (reed_gemm_force_tile, reed_gemm_f32_split, reed_set_cu_reserve, reed_set_concurrent_comm,
+// REED_GEMM_COLSPLIT, REED_GEMM288) — their one definition, in every build of the library.
 int reed_num_cus();            // the device's CUs minus the reserve, at least 32; 256 without a device
 int reed_gemm_forced_tile();
 int reed_concurrent_comm();
+int reed_gemm_f32_split_on();   // reed_gemm_f32_split: always 0 in the 16-bit builds
 GemmKnobs reed_gemm_knobs();

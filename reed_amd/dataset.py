@@ -407,7 +407,7 @@ def convert_image_folder(source_dir, dest_dir, resolution, transform="center-cro
 CONVERT_RESIZE_DEFAULT = "pil"
 
 
-def main(argv=None):
+def build_parser():
     import argparse
     ap = argparse.ArgumentParser(prog="python -m reed_amd.dataset")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -426,8 +426,10 @@ def main(argv=None):
     e.add_argument("source_images_dir")
     e.add_argument("dest_dir")
     e.add_argument("--vae-ckpt", required=True, help="sd-vae-ft-{mse,ema}: a diffusers directory, .safetensors or .bin")
-    e.add_argument("--precision", choices=["fp32", "fp16", "bf16"], default="fp32",
-                   help="GEMM operand type (fp32: exact products; fp16 carries the mantissa of the reference's TF32 convolutions)")
+    e.add_argument("--precision", choices=["fp32", "tf32", "fp16", "bf16"], default="fp32",
+                   help="GEMM operand type (fp32: exact products; fp16 carries the mantissa of the reference's TF32 convolutions; tf32: "
+                        "fp32 operands, activations and range with every product as three bf16 MFMA products, closer to fp32 than "
+                        "TF32 and without fp16's channel-count rule)")
     e.add_argument("--batch-size", type=int, default=8, help="images per encoder call (the files do not depend on it)")
     e.add_argument("--max-images", type=int, default=None)
     e.add_argument("--num-workers", type=int, default=4, help="PNG decode processes (at most 16)")
@@ -449,7 +451,13 @@ def main(argv=None):
     c.add_argument("--num-workers", type=int, default=4, help="decode processes (at most 16)")
     c.add_argument("--vae-sd-dest", default=None, help="also encode every cropped batch into SD-VAE moments here (needs --vae-ckpt)")
     c.add_argument("--vae-ckpt", default=None, help="sd-vae-ft-{mse,ema}: a diffusers directory, .safetensors or .bin")
-    c.add_argument("--precision", choices=["fp32", "fp16", "bf16"], default="fp32", help="the encoder's GEMM operand type")
+    c.add_argument("--precision", choices=["fp32", "tf32", "fp16", "bf16"], default="fp32",
+                   help="the encoder's GEMM operand type (tf32: as for `encode`)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.cmd == "pack":
         m = pack_dataset(a.data_dir, a.out_dir, a.text_embeds_dir, a.features_dirs, with_images=not a.no_images, log_every=10000)

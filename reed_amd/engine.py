@@ -141,11 +141,8 @@ class Engine:
     # ---- forward -------------------------------------------------------------------
     def forward(self, x, t, y, inference, need_grad, drop):
         prec = getattr(self.m, "precision", "bf16")
-        prev = ops.use(prec)
-        try:
+        with ops.build(prec, bool(getattr(self.m, "tf32", False))):
             return self._forward(x, t, y, inference, need_grad, drop, prec)
-        finally:
-            ops.use(prev)
 
     def _forward(self, x, t, y, inference, need_grad, drop, prec):
         m, L = self.m, self.L
@@ -391,6 +388,7 @@ class Engine:
         if getattr(tp, "prec", prec) != prec:
             raise RuntimeError("reed_amd.SiT: model.precision changed between forward and backward")
         prev = ops.use(prec)
+        prev_split = ops.f32_split(bool(getattr(self.m, "tf32", False))) if prec == "fp32" else None
         # gradient buckets are reduced beside this backward's GEMMs (RCCL channels hold CUs): only then does the library keep to
         # kernels that degrade gracefully without every CU (csrc/gemm_plan.cpp:reed_set_concurrent_comm); the forward, the
         # optimiser and the sampler run with no collective in flight (the step waits for the last bucket before the update)
@@ -402,6 +400,8 @@ class Engine:
         finally:
             if comm:
                 ops.set_concurrent_comm(False)
+            if prev_split is not None:
+                ops.f32_split(prev_split)
             ops.use(prev)
 
     def _backward(self, tp, dout, dzs, hdt):

@@ -95,10 +95,12 @@ def build_parser():
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft-{ema,mse} checkpoint (diffusers directory or its diffusion_pytorch_model file): "
                              "decode with the in-repo decoder instead of the diffusers package")
-    parser.add_argument("--sample-precision", type=str, choices=["fp16", "bf16", "fp32"], default=None,
+    parser.add_argument("--sample-precision", type=str, choices=["fp16", "bf16", "fp32", "tf32"], default=None,
                         help="operand type of the model evaluations: fp16 = 10-bit mantissa (the reference's TF32; the default "
                              "with --tf32), fp32 = the reference's --no-tf32 arithmetic (the default with --no-tf32), bf16 = the "
-                             "training precision")
+                             "training precision, tf32 = fp32 operands and range with every GEMM product taken as three bf16 MFMA "
+                             "products (closer to fp32 than TF32; no half-precision overflow, so no re-sampling fallback), for the "
+                             "model and the VAE decoder alike")
     return parser
 
 
@@ -112,15 +114,16 @@ def sample_precision(args):
 def decode_latents(vae, z, args):
     """`vae.decode(z).sample` (generate.py:156).  The in-repo decoder runs on the HIP kernels with the operand type the
     reference's flags mean here: fp16 operands + fp32 accumulation and activations under --tf32 (TF32's mantissa; the reference's
-    convolutions are TF32 there), exact fp32 under --no-tf32.  A non-finite fp16 result (half saturates at 65504, TF32 does
-    not) is decoded again with fp32 operands."""
+    convolutions are TF32 there), exact fp32 under --no-tf32, the fp32 pass on the split GEMM under --sample-precision tf32.
+    A non-finite fp16 result (half saturates at 65504, TF32 does not) is decoded again with fp32 operands."""
     from .vae import SDVAEDecoder
     if not isinstance(vae, SDVAEDecoder):
         img = vae.decode(z)
         return getattr(img, "sample", img)        # diffusers returns a DecoderOutput
-    prec = "fp32" if sample_precision(args) == "fp32" else "fp16"
+    prec = sample_precision(args)
+    prec = prec if prec in ("fp32", "tf32") else "fp16"
     img = vae.decode(z, precision=prec)
-    if prec != "fp32" and not bool(torch.isfinite(img).all()):
+    if prec == "fp16" and not bool(torch.isfinite(img).all()):
         import warnings
         warnings.warn("reed_amd.generate: non-finite images from the fp16-operand VAE decoder; decoding this batch with fp32 operands")
         img = vae.decode(z, precision="fp32")
@@ -188,7 +191,8 @@ def main(args):
             state_dict.pop(k)
     model.load_state_dict(state_dict, strict=False)
     model.eval()
-    model.precision = sample_precision(args)
+    from . import ops
+    model.precision, model.tf32 = ops.build_of(sample_precision(args))   # "tf32" = the fp32 build with the split GEMM
     assert args.cfg_scale >= 1.0, "In almost all cases, cfg_scale be >= 1.0"
     if args.cfg_scale > 1.0:
         assert args.num_classes == 1000, "the samplers hard-code the null class id 1000 (samplers.py:59)"

@@ -97,6 +97,9 @@ class SiT(nn.Module):
         # training with the on-device GradScaler; csrc/common.hpp REED_FP16) or "fp32" (fp32 operands and activations on the
         # fp32 MFMA: --mixed-precision no / generate.py --no-tf32; REED_FP32)
         self.precision = "bf16"
+        # at precision "fp32" only: every fp32 GEMM product as three bf16 MFMA products (ops.f32_split: --allow-tf32 /
+        # --sample-precision tf32); the engine applies it beside ops.use("fp32") and restores it.  The attention stays exact fp32.
+        self.tf32 = False
 
     # ------------------------------------------------------------------ structure
     def _param_shapes(self):

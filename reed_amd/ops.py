@@ -222,6 +222,58 @@ def forced_tile(tile):
         gemm_force_tile(prev)
 
 
+_F32_SPLIT = False
+
+
+def f32_split(on):
+    """The fp32 build's matrix arithmetic (reed_gemm_f32_split): False = exact fp32 products, True = every fp32 product as three
+    bf16 MFMA products with fp32 accumulation (the reference's --allow-tf32 / generate.py --tf32 on hardware without an xf32
+    instruction): reed_gemm, reed_conv3x3 and reed_conv3x3_down of the "fp32" build; its attention stays exact.  Process-wide,
+    like the forced tile.  Returns the previous setting."""
+    global _F32_SPLIT
+    prev, on = _F32_SPLIT, bool(on)
+    if on != prev:
+        L = _lib.load("fp32")
+        _lib.check(L.reed_gemm_f32_split(int(on)), "reed_gemm_f32_split", L)
+        _F32_SPLIT = on
+    return prev
+
+
+def f32_split_on():
+    return _F32_SPLIT
+
+
+@contextlib.contextmanager
+def f32_split_mode(on):
+    """f32_split(on) for the block; after it — also when the block raises — the setting from before."""
+    prev = f32_split(on)
+    try:
+        yield
+    finally:
+        f32_split(prev)
+
+
+def build_of(precision):
+    """(library build, split mode) of a precision as the public surface names it: "tf32" is the "fp32" build with f32_split on;
+    "bf16" / "fp16" / "fp32" are themselves with it off.  ("tf32" is not a fourth build: _lib.PRECISIONS and precision_of(dtype)
+    know three.)"""
+    return ("fp32", True) if precision == "tf32" else (precision, False)
+
+
+@contextlib.contextmanager
+def build(precision, tf32=False):
+    """use(precision) for the block and, at "fp32", f32_split(tf32); both restored after it.  What a forward / backward / VAE pass
+    runs under: `tf32` means something at "fp32" only (the 16-bit builds' operands are 16-bit already)."""
+    prev = use(precision)
+    prev_split = f32_split(tf32) if precision == "fp32" else None
+    try:
+        yield
+    finally:
+        if prev_split is not None:
+            f32_split(prev_split)
+        use(prev)
+
+
 WGRAD_SLOTS = 512  # resident 128x128 blocks: 256 CUs x 2 (64 KiB LDS, <=128 VGPRs... see gemm.hip launch bounds)
 _CU_RESERVE = 0
 
@@ -330,6 +382,8 @@ def wgrad_group_deal(shapes, cus=256, precision="bf16"):
 
 
 GEMM_KERNELS = ("128", "144", "288", "256x8", "256w", "256wp", "skinny", "tn_tall", "tn_wide", "f32")
+# kernel id 10 (GK_F32_SPLIT), kept out of the tuple above: that one lists what the tile knobs select between, one kernel per name
+GEMM_KERNEL_F32_SPLIT = "f32_split"
 
 
 def gemm_plan(lay, epi, M, N, K, split_k=1, *, dbias=False, slab=False, dot_operands=True, rows_per_gate=1, ncu=0, forced=0,
@@ -337,7 +391,7 @@ def gemm_plan(lay, epi, M, N, K, split_k=1, *, dbias=False, slab=False, dot_oper
     """Which kernels reed_gemm(lay, epi, M, N, K, split_k) launches, on which part of the output (reed_gemm_plan: host arithmetic,
     runs without a GPU).  ncu = 0: the CUs the library plans for now; colsplit / use288 = -1: as the environment set them.
     Returns (0, [launch, ...]) with launch = dict(kernel=GEMM_KERNELS name, row0, rows, col0, cols, splits, ksplit_len, tile_gm,
-    grid), or (reed_gemm's error code, [])."""
+    grid), or (reed_gemm's error code, []).  precision "fp32": kernel "f32", or "f32_split" while f32_split(True) holds."""
     out = (ctypes.c_int * 27)()
     n = _lib.load(precision).reed_gemm_plan(int(lay), int(epi), int(M), int(N), int(K), int(split_k),
                                             int(bool(dbias)) | 2 * int(bool(slab)) | 4 * int(bool(dot_operands)), int(rows_per_gate),
@@ -348,7 +402,7 @@ def gemm_plan(lay, epi, M, N, K, split_k=1, *, dbias=False, slab=False, dot_oper
     keys = ("kernel", "row0", "rows", "col0", "cols", "splits", "ksplit_len", "tile_gm", "grid")
     launches = [dict(zip(keys, out[9 * i:9 * i + 9])) for i in range(n)]
     for l in launches:
-        l["kernel"] = GEMM_KERNELS[l["kernel"]]
+        l["kernel"] = GEMM_KERNELS[l["kernel"]] if l["kernel"] < len(GEMM_KERNELS) else GEMM_KERNEL_F32_SPLIT
     return 0, launches
 
 

@@ -62,7 +62,12 @@ def parse_args(input_args=None):
     parser.add_argument("--resolution", type=int, choices=[256, 512], default=256)
     parser.add_argument("--batch-size", type=int, default=256)
     # precision
-    parser.add_argument("--allow-tf32", action="store_true")
+    parser.add_argument("--allow-tf32", action="store_true",
+                        help="with --mixed-precision no: the fp32 GEMMs (forward, input and weight gradients) take every product as "
+                             "three bf16 MFMA products with fp32 accumulation (csrc/gemm_f32.hip: fp32 operands and range, an error "
+                             "of 3 * 2^-16 per product against TF32's 2^-10, several times the exact fp32 rate); the attention stays "
+                             "exact fp32.  Without effect under fp16 / bf16, whose GEMM operands are 16-bit already (in the "
+                             "reference the flag then reaches only operations outside autocast)")
     parser.add_argument("--mixed-precision", type=str, default="fp16", choices=["no", "fp16", "bf16"])
     # optimization
     parser.add_argument("--epochs", type=int, default=1400)
@@ -125,6 +130,7 @@ def parse_args(input_args=None):
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
     args.encoder_precision = resolve_encoder_precision(args.encoder_precision, args.mixed_precision)   # args.json holds the result
+    args.gemm_tf32 = resolve_tf32(args.allow_tf32, args.mixed_precision)                               # and this one
     if args.encoder_ckpts and args.resolution != 256:
         from .encoders import vit_resolution_error
         items = [] if args.enc_type in (None, "None") else args.enc_type.split(",")
@@ -135,6 +141,11 @@ def parse_args(input_args=None):
                          f"towers run at 448 pixels); {'; '.join(why)}. At --resolution {args.resolution} pass --features-dirs, "
                          f"--packed-dir with features, or --synthetic")
     return args
+
+
+def resolve_tf32(allow_tf32, mixed_precision):
+    """Whether --allow-tf32 selects the split fp32 GEMM (SiT.tf32): only where the GEMM operands are fp32, --mixed-precision no."""
+    return bool(allow_tf32) and mixed_precision == "no"
 
 
 def resolve_encoder_precision(encoder_precision, mixed_precision):
@@ -274,12 +285,20 @@ def main(args):
     # (libreed_hip_f32.so, csrc/gemm_f32.hip: 1/16 of the 16-bit MFMA rate — the reference's own fp32 mode is as slow relative
     # to its autocast modes).
     model.precision = {"no": "fp32"}.get(args.mixed_precision, args.mixed_precision)
+    # --allow-tf32 with "no" (train.py:249-251 sets torch.backends.cuda.matmul.allow_tf32): the fp32 GEMMs as three bf16 MFMA products
+    allow_tf32 = getattr(args, "allow_tf32", False)
+    model.tf32 = getattr(args, "gemm_tf32", resolve_tf32(allow_tf32, args.mixed_precision))
     ema = copy.deepcopy(model).to(device)
     ema.requires_grad_(False)
     loss_fn = SILoss(prediction=args.prediction, path_type=args.path_type, enc_names=enc_names,
                      weighting=args.weighting, loss_weights={n: args.repa_coeff[i] for i, n in enumerate(enc_names)},
                      time_schedule=args.time_schedule, cutoffs=args.cutoffs, latents_scale=0.18215, latents_bias=0.0)
     logger.info(f"SiT Parameters: {sum(p.numel() for p in model.parameters()):,}")
+    if model.tf32:
+        logger.info("--allow-tf32: fp32 GEMMs (forward, input and weight gradients) run as three bf16 MFMA products per fp32 product, "
+                    "fp32 accumulation; attention, LayerNorm, loss and optimiser stay exact fp32")
+    elif allow_tf32:
+        logger.info(f"--allow-tf32 has no effect with --mixed-precision {args.mixed_precision}: the GEMM operands are 16-bit")
     logger.info(f"Encoders for Alignment {enc_names}; weights {args.repa_coeff}")
     if encoders:
         logger.info(f"frozen encoders: {', '.join(args.enc_type.split(','))} at {args.encoder_precision}")

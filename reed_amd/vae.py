@@ -193,7 +193,10 @@ class SDVAEEncoder(nn.Module):
         """raw u8 [B, 3, H, W] on the GPU -> moments f32 [B, 8, H / 8, W / 8], on the HIP kernels.  precision = the GEMM operand
         type: "fp32" (default: exact fp32 products), "fp16" / "bf16" (the 16-bit MFMA convolutions; channel counts must then be
         multiples of 128).  The reference encodes in fp32 with PyTorch's default TF32 convolutions, whose operands keep 10
-        mantissa bits: fp16 operands carry the same mantissa, so "fp16" is the closest cheap match, "fp32" an exact superset."""
+        mantissa bits: fp16 operands carry the same mantissa, so "fp16" is the closest cheap match, "fp32" an exact superset.
+        "tf32": the fp32 pass (fp32 operands and activations, any channel count that is a multiple of 4) with every product of the
+        GEMMs and of the convolutions' window gather taken as three bf16 MFMA products (ops.f32_split): fp32's range, closer to
+        fp32 than TF32 itself, several times the exact pass's rate."""
         ops.require_cuda(raw, "images")
         if getattr(self, "_hip", None) is None:
             self._hip = _HipEncode(self)
@@ -222,7 +225,8 @@ class SDVAEDecoder(nn.Module):
     def decode(self, z, precision="fp32"):
         """z [B, 4, h, w] on the GPU -> images f32 [B, 3, 8h, 8w], on the HIP kernels.  precision = the GEMM operand type:
         "fp32" (default: exact fp32 products, the reference's `--no-tf32` arithmetic and a superset of its TF32 default),
-        "fp16" / "bf16" (the 16-bit MFMA kernels; channel counts must then be multiples of 128, as the published config's are)."""
+        "fp16" / "bf16" (the 16-bit MFMA kernels; channel counts must then be multiples of 128, as the published config's are),
+        "tf32" (the fp32 pass with ops.f32_split on: see SDVAEEncoder.encode)."""
         ops.require_cuda(z, "latents")
         if getattr(self, "_hip", None) is None:
             self._hip = _HipDecode(self)
@@ -383,8 +387,8 @@ class _HipDecode(_HipVAE):
 
     def decode(self, z, precision="fp32"):
         v, d = self.vae, self.vae.decoder
-        prev = ops.use(precision)
-        try:
+        precision, tf32 = ops.build_of(precision)
+        with ops.build(precision, tf32):
             x = z.detach().float().permute(0, 2, 3, 1).contiguous()                       # NHWC
             if x.shape[-1] % 4:
                 raise ValueError("latent channels must be a multiple of 4")
@@ -404,8 +408,6 @@ class _HipDecode(_HipVAE):
                     x = self._conv(x, f"decoder.up_blocks.{i}.upsamplers.0.conv", u.upsamplers[0].conv, precision, 9, up=True)
             y = self._conv(x, "decoder.conv_out", d.conv_out, precision, 9, norm=d.conv_norm_out, silu=True)
             return y[..., :d.conv_out.out_channels].permute(0, 3, 1, 2).contiguous()
-        finally:
-            ops.use(prev)
 
 
 class _HipEncode(_HipVAE):
@@ -438,9 +440,9 @@ class _HipEncode(_HipVAE):
             raise ValueError("reed_vae_moments takes 8 moment channels (latent_channels = 4)")
         raw = raw.contiguous()
         B = raw.shape[0]
-        prev = ops.use(precision)
+        precision, tf32 = ops.build_of(precision)
         pin = precision != "fp32" and ops.gemm_forced_tile() != 128
-        try:
+        with ops.build(precision, tf32):
             with ops.forced_tile(128) if pin else contextlib.nullcontext():
                 x = self._image_conv(raw, precision)
                 if x.shape[-1] != e.conv_in.out_channels:
@@ -462,8 +464,6 @@ class _HipEncode(_HipVAE):
                 ops.vae_moments(y, ldc, B, h, w, q.weight.detach().float().reshape(8, 8).contiguous(),
                                 q.bias.detach().float().contiguous(), out)
                 return out
-        finally:
-            ops.use(prev)
 
 
 # attention parameters of the checkpoints published before diffusers renamed them (its loader converts these names too)

@@ -3,7 +3,7 @@ against the same module on torch's operators (MIOpen convolutions, fp32), publis
 images at 256^2 (-> [8, 32, 32]) and 512^2 (-> [8, 64, 64], T = 4096 in the mid-block attention).  Device events around `reps`
 calls after one warm-up call per form.  FLOP per image: the unpadded contractions (every convolution and Linear, the two attention
 products), counted from the module's shapes.
-usage (GPU box): python tools/time_vae_encode.py [--batch 8] [--reps 3]"""
+usage (GPU box): python tools/time_vae_encode.py [--batch 8] [--reps 3] [--resolutions 256,512]"""
 import argparse
 import sys
 
@@ -50,6 +50,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--resolutions", default="256,512")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -58,11 +59,11 @@ def main():
         p.data.normal_(0, 0.02)
     enc = enc.to(dev)
     print(f"{torch.cuda.get_device_name(0)}, batch {a.batch}, {a.reps} timed calls per form")
-    for res in (256, 512):
+    for res in [int(r) for r in a.resolutions.split(",")]:
         flop = flop_per_image(enc, res)
         raw = torch.randint(0, 256, (a.batch, 3, res, res), dtype=torch.uint8, device=dev)
         print(f"{res}^2 -> [8, {res // 8}, {res // 8}]: {flop / 1e9:.1f} GFLOP per image (unpadded contractions)")
-        for prec in ("fp32", "fp16", "bf16"):
+        for prec in ("fp32", "tf32", "fp16", "bf16"):
             t = timed(lambda: enc.encode(raw, precision=prec), a.reps)
             print(f"  HIP {prec}: {t * 1e3 / a.batch:8.2f} ms / image, {a.batch / t:8.1f} images/s, {flop * a.batch / t / 1e12:7.1f} TFLOP/s")
         x = raw.float() / 127.5 - 1
