@@ -16,7 +16,8 @@
 // Backward recomputes P from the saved log-sum-exp, key-stationary (a wave owns 32 keys: dK / dV in registers, S and dP
 // once) with dQ^T = K^T dS^T formed every 64 queries through an LDS tile of dS^T; deterministic, no atomics.  Kernels in
 // this file: attn_fwd_kernel (any T; <64, true>: a <= 16-row tail past 512 keys) + attn_fwd_rows_kernel (a <= 16-row tail), attn_fwd256p_kernel (T <= 256, persistent:
-// the engine's forward), attn_bwd_ks_kernel (one shot), attn_bwd_ksp_kernel (persistent, T < 256), attn_bwd_ring_kernel
+// the engine's forward; at head_dim 72 — ONES, here and in attn_fwd256v_kernel — lse is the log of the 16-bit-ROUNDED row sum: tests/attention_ref.py),
+// attn_bwd_ks_kernel (one shot), attn_bwd_ksp_kernel (persistent, T < 256), attn_bwd_ring_kernel
 // (persistent with Q / dO rings, T = 256: the engine's backward), attn_bwd_long_kernel + attn_dq_reduce_kernel (persistent,
 // 256 < T <= 4096: 512^2 training).  Forms that were measured and removed are named where
 // they stood (round 2's three-barrier forward, round 1's two-phase backward, the half-workgroup stagger).

@@ -7,6 +7,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _ref(qkv, B, T, H, hd):
+    """fp32 softmax attention and logsumexp.  The lse tolerance of the tests below has to know one thing about the kernels: at
+    hd 72 and T <= 256 the forward (attn_fwd256p_kernel<72> / attn_fwd256v_kernel<72>, ONES) takes the softmax denominator from a
+    ones column in V, so lse is the log of the sum of the 16-bit-ROUNDED p — one 16-bit ulp relative of l, 2**-7 in bf16, not an
+    fp32 rounding.  tests/attention_ref.py derives the budget; tests/test_attention_ref_gpu.py holds every path to it."""
     q, k, v = qkv.float().reshape(B, T, 3, H, hd).permute(2, 0, 3, 1, 4).unbind(0)
     s = (q @ k.transpose(-1, -2)) * hd ** -0.5
     p = s.softmax(-1)
