@@ -196,6 +196,15 @@ int reed_qk_norm_bwd(const void* dn, const void* qkv, const float* stats, const 
 /* PatchEmbed (timm, sit.py:198-200,279): tokens f32 [B,T,D] = bf16(conv_p(x bf16, W bf16)+b) + pos_embed f32 */
 int reed_patch_embed_fwd(const float* x, const void* w, const void* bias, const float* pos,
                          float* tokens, int B, int C, int HW, int P, int D, void* stream);
+/* PatchEmbed, input gradient (what autograd gives the reference through F.conv2d): for token bt = (b, ph, pw) and
+ * k = (c, pi, pj)   dx f32 [B,C,HW,HW] at [b, c, ph*P+pi, pw*P+pj] = sum_d r(dtok[bt, d]) * w[d, k].
+ * dtok is the f32 token-stream gradient [B*T, D], rounded to the operand type on load (r; the identity in the fp32 build) exactly
+ * as reed_smallk_wgrad reads it with wide_is_f32 = 1; w is the stored operand-type weight [D, C*P*P].  fp32 accumulation in a
+ * fixed order (two runs: the same bits).  The stride is the patch size, so every element of dx is written exactly once: no
+ * atomics, no zero fill, nothing past the end.  C*P*P = 16 with D % 4 == 0, D <= 1280 and 16-byte aligned dtok / w streams
+ * dtok once at 16 bytes per lane; anything else reed_patch_embed_fwd accepts takes a generic form.  Shapes outside that domain
+ * (HW % P, C*P*P % 8, a non-positive extent) are refused without a launch. */
+int reed_patch_embed_bwd_x(const float* dtok, const void* w, float* dx, int B, int C, int HW, int P, int D, void* stream);
 /* patchify to bf16 rows: out bf16 [B*T, C*P*P]; order 0 = (c,pi,pj) (conv input, timm PatchEmbed),
  * order 1 = (pi,pj,c) (the unpatchify order of sit.py:256-269) */
 int reed_patchify_bf16(const float* x, void* out, int B, int C, int HW, int P, int order, void* stream);
@@ -209,6 +218,11 @@ int reed_smallk_wgrad(const void* wide, int wide_is_f32, const void* small, floa
                       int accumulate, void* stream);
 /* TimestepEmbedder.positional_embedding (sit.py:45-64): out bf16 [B, dim] = [cos(t f) | sin(t f)] */
 int reed_timestep_sinusoid(const float* t, void* out, int B, int dim, float max_period, void* stream);
+/* its derivative with respect to t: dt f32 [B], dt[b] = sum_{k < dim/2} f_k * (cos(t f_k) * dsin[b, dim/2 + k] - sin(t f_k) * dsin[b, k])
+ * with f_k and t f_k formed by the forward's own expressions; dsin f32 [B, dim] is the gradient with respect to the (unrounded)
+ * table, the padding column of an odd dim contributes nothing.  One fixed-order reduction per sample.  B <= 0 or dim < 2 is
+ * refused without a launch. */
+int reed_timestep_sinusoid_bwd(const float* t, const float* dsin, float* dt, int B, int dim, float max_period, void* stream);
 /* LabelEmbedder (sit.py:84-99): labels_out = drop ? num_classes : labels; c_out f32 [B,D] = t_emb bf16 + table f32[label];
  * silu_c bf16 [B,D] = bf16(silu(c)) (input of every adaLN linear, sit.py:126-129). table has table_rows rows; a label
  * outside [0, table_rows) (nn.Embedding raises, sit.py:98) is replaced by row 0 and *err_flag (device int, may be NULL)
@@ -217,7 +231,7 @@ int reed_label_cond(const int64_t* labels, const uint8_t* drop, int num_classes,
                     const void* t_emb, int64_t* labels_out, float* c, void* silu_c, int* err_flag, int B, int D,
                     void* stream);
 /* backward of the conditioning vector: dc f32 [B,D] -> dt_emb bf16, dtable f32 [rows,D] += (deterministic scatter;
- * dsilu_c is the f32 grad w.r.t. silu(c), bf16-rounded inside) */
+ * dsilu_c is the f32 grad w.r.t. silu(c), bf16-rounded inside).  dtable may be NULL (a frozen table): dt_emb alone, same bits. */
 int reed_label_cond_bwd(const float* dsilu_c, const float* c, const int64_t* labels_eff, void* dt_emb,
                         float* dtable, int B, int D, void* stream);
 /* FinalLayer + unpatchify (sit.py:140-158,256-269): out f32 [B,C,HW,HW] */

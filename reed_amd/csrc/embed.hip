@@ -122,6 +122,118 @@ __global__ __launch_bounds__(PNT) void patch_embed_fwd16_kernel(const float* __r
   }
 }
 
+// ---- patch embed backward, input gradient: dx[b, c, ph P + pi, pw P + pj] = sum_d r(dtok[bt, d]) w[d, k], k = (c, pi, pj) ----
+// The convolution's stride is its kernel size: every element of dx belongs to exactly one (token, k), so each is written once, with
+// a plain store.  dtok is the fp32 token-stream gradient, rounded to the operand type on load as smallk_wgrad_kernel<true, .> reads
+// the same array (products exact in fp32 in the 16-bit builds).
+//
+// K = 16 (patch 2 on 4 channels): one pass over dtok at 16 bytes per lane.  The [D, 16] weight sits in LDS, a wave takes two tokens
+// at a time (each weight read feeds two FMAs), a lane the columns d = 4 (lane + 64 j) + e of its 16-byte loads: one fp32 chain per
+// lane and k over its columns in ascending order, then a butterfly over the lane bits 5 .. 0 that halves the values a lane holds
+// at every level (2 x 16 -> 16 -> 8 -> 4 -> 2 -> 1: 31 exchanges for a pair of tokens plus the last level, where 6 x 32 full
+// wave sums would take 192).  A sum l + (l ^ m) has the same bits on both lanes, so the result does not depend on which lane keeps
+// which half: value (token, k) = the 64 lane chains reduced by halves, 32 + 32, 16 + 16, ... (tests/input_grad_ref.py restates it).
+// LDS layout: the 8-element half h of row d = 4 q + e at ((((q >> 6) * 4 + e) * 2 + h) * 64 + (q & 63)) * 8: the 64 lanes of a
+// wave read 64 consecutive 16-byte slots (16-bit builds), conflict-free.
+constexpr int BX_NT = 256, BX_PT = 32, BX_MAXJ = 5;   // threads, tokens per block, 16-byte loads per lane and row (D <= 1280)
+__device__ __forceinline__ int bx_lds_off(int d, int h) {
+  const int q = d >> 2, e = d & 3;
+  return ((((q >> 6) * 4 + e) * 2 + h) * 64 + (q & 63)) * 8;
+}
+// one level of the butterfly: 2 n values in, n out; lanes whose bit `m` is set keep the upper half
+template <int n>
+__device__ __forceinline__ void bx_halve(float* v, int m, bool up) {
+#pragma unroll
+  for (int i = 0; i < n; ++i) {
+    const float keep = up ? v[i + n] : v[i], send = up ? v[i] : v[i + n];
+    v[i] = keep + __shfl_xor(send, m, 64);
+  }
+}
+__global__ __launch_bounds__(BX_NT) void patch_embed_bwd_x16_kernel(const float* __restrict__ dtok, const bf16* __restrict__ w,
+                                                                    float* __restrict__ dx, int B, int C, int HW, int P, int D) {
+  extern __shared__ __attribute__((aligned(16))) char bx_raw[];
+  bf16* wl = (bf16*)bx_raw;
+  const int G = HW / P, T = G * G, nv = D >> 2;
+  const long BT = (long)B * T, bt0 = (long)blockIdx.x * BX_PT;
+  for (int c = threadIdx.x; c < 2 * D; c += BX_NT)            // chunk c = the half (c & 1) of weight row c >> 1
+    *(bf16x8*)(wl + bx_lds_off(c >> 1, c & 1)) = *(const bf16x8*)(w + (long)c * 8);
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int p = wave; p < BX_PT / 2; p += BX_NT / 64) {
+    const long ta = bt0 + 2 * p;
+    if (ta >= BT) break;
+    const bool two = ta + 1 < BT;
+    const float* ra = dtok + ta * D;
+    const float* rb = dtok + (two ? ta + 1 : ta) * D;        // a single last token: read twice, the second result dropped
+    f32x4 ga[BX_MAXJ], gb[BX_MAXJ];
+#pragma unroll
+    for (int j = 0; j < BX_MAXJ; ++j) {
+      const int q = lane + 64 * j;
+      if (q < nv) { ga[j] = *(const f32x4*)(ra + 4 * q); gb[j] = *(const f32x4*)(rb + 4 * q); }
+    }
+    float v[32];                                              // [0, 16): token a, [16, 32): token b
+#pragma unroll
+    for (int k = 0; k < 32; ++k) v[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < BX_MAXJ; ++j) {
+      const int q = lane + 64 * j;
+      if (q < nv) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float xa = bfround(ga[j][e]), xb = bfround(gb[j][e]);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bf16x8 wv = *(const bf16x8*)(wl + (((j * 4 + e) * 2 + h) * 64 + lane) * 8);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              const float wf = bf2f(wv[i]);
+              v[8 * h + i] = fmaf(xa, wf, v[8 * h + i]);
+              v[16 + 8 * h + i] = fmaf(xb, wf, v[16 + 8 * h + i]);
+            }
+          }
+        }
+      }
+    }
+    bx_halve<16>(v, 32, lane & 32);    // lanes 32 .. 63 go on with token b
+    bx_halve<8>(v, 16, lane & 16);     // k bit 3
+    bx_halve<4>(v, 8, lane & 8);
+    bx_halve<2>(v, 4, lane & 4);
+    bx_halve<1>(v, 2, lane & 2);
+    const float r = v[0] + __shfl_xor(v[0], 1, 64);
+    const long bt = ta + (lane >> 5);
+    if (!(lane & 1) && bt < BT) dx[patch_src((int)(bt / T), (int)(bt % T), (lane >> 1) & 15, C, HW, P, 0)] = r;
+  }
+}
+
+// Any K (a multiple of 8: patches 4 and 8 of the preset table have K = 64 and 256) and any D: a wave per token, a lane the columns
+// d = lane + 64 i, 8 values of k at a time with the weights from global memory (L2); the row of dtok is read again for every 8 k
+// (from L1).  The same tree: a chain per lane over its columns in ascending order, then the halves 32 + 32, 16 + 16, ...
+__global__ __launch_bounds__(256) void patch_embed_bwd_x_kernel(const float* __restrict__ dtok, const bf16* __restrict__ w,
+                                                                float* __restrict__ dx, int B, int C, int HW, int P, int D) {
+  const int G = HW / P, T = G * G, K = C * P * P;
+  const long BT = (long)B * T, bt = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bt >= BT) return;
+  const int lane = threadIdx.x & 63, b = (int)(bt / T), t = (int)(bt % T);
+  const float* row = dtok + bt * D;
+  for (int k0 = 0; k0 < K; k0 += 8) {
+    float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int d = lane; d < D; d += 64) {
+      const float g = bfround(row[d]);
+      const bf16x8 wv = *(const bf16x8*)(w + (long)d * K + k0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = fmaf(g, bf2f(wv[i]), acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = wave_sum(acc[i]);
+    if (lane < 8) {
+      float r = acc[0];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) r = lane == i ? acc[i] : r;
+      dx[patch_src(b, t, k0 + lane, C, HW, P, 0)] = r;
+    }
+  }
+}
+
 // ---- small-K weight gradient (final layer: KS = 2*C*p*p = 32, patch embed: KS = C*p*p = 16 at patch 2), stage 1 ----
 // out[d][k] = sum_m wide[m][d] * small[m][k] over a token slice; ws[slice] holds the partial out (layout 0: d*KS+k,
 // 1: k*Dw+d), then the partial colsum(wide)[Dw], then the partial colsum(small)[KS].
@@ -237,6 +349,23 @@ __global__ void sinusoid_kernel(const float* __restrict__ t, bf16* __restrict__ 
   out[(long)b * dim + half + k] = f2bf(sinf(arg));
   if ((dim & 1) && k == 0) out[(long)b * dim + dim - 1] = f2bf(0.f);
 }
+// dt[b] = sum_k f_k (cos(arg) dsin[b, half + k] - sin(arg) dsin[b, k]), f_k and arg formed as above; the padding column of an odd
+// dim is a constant.  A wave per sample: a chain per lane over k = lane, lane + 64, ..., then the halves 32 + 32, 16 + 16, ...
+__global__ __launch_bounds__(64) void sinusoid_bwd_kernel(const float* __restrict__ t, const float* __restrict__ dsin,
+                                                          float* __restrict__ dt, int dim, float max_period) {
+  const int half = dim / 2, b = blockIdx.x;
+  const float* g = dsin + (long)b * dim;
+  const float tb = t[b];
+  float acc = 0.f;
+  for (int k = threadIdx.x; k < half; k += 64) {
+    float a = (float)(-log((double)max_period)) * (float)k;
+    float f = expf(a / (float)half);
+    float arg = tb * f;
+    acc += f * (cosf(arg) * g[half + k] - sinf(arg) * g[k]);
+  }
+  acc = wave_sum(acc);
+  if (threadIdx.x == 0) dt[b] = acc;
+}
 
 // ---- label embedding + conditioning ----
 // A label outside [0, table_rows) (nn.Embedding raises there, sit.py:98) must not index past the table: the table lives
@@ -268,7 +397,7 @@ __global__ void label_cond_bwd_kernel(const float* __restrict__ dsilu, const flo
   for (int b = 0; b < B; ++b) {  // sequential over the batch: deterministic scatter-add
     float g = bfround(dsilu[(long)b * D + d]) * silu_grad_f(c[(long)b * D + d]);
     dt_emb[(long)b * D + d] = f2bf(g);
-    dtable[labels_eff[b] * D + d] += g;
+    if (dtable) dtable[labels_eff[b] * D + d] += g;   // null: a frozen table (Engine: the frozen-weight backward)
   }
 }
 
@@ -555,6 +684,30 @@ extern "C" int reed_patch_embed_fwd(const float* x, const void* w, const void* b
   return REED_OK;
 }
 
+extern "C" int reed_patch_embed_bwd_x(const float* dtok, const void* w, float* dx, int B, int C, int HW, int P, int D,
+                                      void* stream) {
+  REED_CHECK_ARG(dtok && w && dx, "patch_embed_bwd_x: null pointer");
+  REED_CHECK_ARG(B > 0 && C > 0 && P > 0 && D > 0 && HW > 0, "patch_embed_bwd_x: bad B=%d C=%d HW=%d P=%d D=%d", B, C, HW, P, D);
+  REED_CHECK_ARG(HW % P == 0 && (C * P * P) % 8 == 0, "patch_embed: HW=%d P=%d C=%d unsupported", HW, P, C);
+  const long BT = (long)B * (HW / P) * (HW / P);
+  const int K = C * P * P;
+  if (K == PK && D % 4 == 0 && D <= 4 * 64 * BX_MAXJ && ((uintptr_t)w % 16) == 0 && ((uintptr_t)dtok % 16) == 0) {
+    const int lds = cdiv(D / 4, 64) * 4096 * (int)sizeof(bf16);   // whole groups of 64 16-byte loads: see bx_lds_off
+    if (lds > 64 * 1024) {   // the fp32 build above D = 1024: more dynamic LDS than a launch may ask for without the attribute
+      hipError_t e = hipFuncSetAttribute((const void*)patch_embed_bwd_x16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) { reed_set_error("hipFuncSetAttribute(LDS=%d): %s", lds, hipGetErrorString(e)); return (int)e; }
+    }
+    REED_KLAUNCH(patch_embed_bwd_x16_kernel, dim3(cdiv(BT, BX_PT)), dim3(BX_NT), (size_t)lds, (hipStream_t)stream, dtok,
+                 (const bf16*)w, dx, B, C, HW, P, D);
+    REED_LAUNCH_CHECK();
+    return REED_OK;
+  }
+  REED_KLAUNCH(patch_embed_bwd_x_kernel, dim3(cdiv(BT, 4)), dim3(256), 0, (hipStream_t)stream, dtok, (const bf16*)w, dx, B, C, HW,
+               P, D);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
 extern "C" int64_t reed_smallk_wgrad_ws_floats(int Dw, int KS) { return (int64_t)NSL * ((int64_t)KS * Dw + Dw + KS); }
 
 extern "C" int reed_smallk_wgrad(const void* wide, int wide_is_f32, const void* small, float* ws, float* out,
@@ -588,6 +741,14 @@ extern "C" int reed_timestep_sinusoid(const float* t, void* out, int B, int dim,
   return REED_OK;
 }
 
+extern "C" int reed_timestep_sinusoid_bwd(const float* t, const float* dsin, float* dt, int B, int dim, float max_period,
+                                          void* stream) {
+  REED_CHECK_ARG(t && dsin && dt && B > 0 && dim >= 2, "timestep_sinusoid_bwd: bad args");
+  REED_KLAUNCH(sinusoid_bwd_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, t, dsin, dt, dim, max_period);
+  REED_LAUNCH_CHECK();
+  return REED_OK;
+}
+
 extern "C" int reed_label_cond(const int64_t* labels, const uint8_t* drop, int num_classes, int table_rows,
                                const float* table, const void* t_emb, int64_t* labels_out, float* c, void* silu_c,
                                int* err_flag, int B, int D, void* stream) {
@@ -602,7 +763,7 @@ extern "C" int reed_label_cond(const int64_t* labels, const uint8_t* drop, int n
 
 extern "C" int reed_label_cond_bwd(const float* dsilu_c, const float* c, const int64_t* labels_eff, void* dt_emb,
                                    float* dtable, int B, int D, void* stream) {
-  REED_CHECK_ARG(dsilu_c && c && labels_eff && dt_emb && dtable, "label_cond_bwd: null pointer");
+  REED_CHECK_ARG(dsilu_c && c && labels_eff && dt_emb, "label_cond_bwd: null pointer");
   REED_KLAUNCH(label_cond_bwd_kernel, dim3(cdiv(D, 256)), dim3(256), 0, (hipStream_t)stream, dsilu_c, c,
                      labels_eff, (bf16*)dt_emb, dtable, B, D);
   REED_LAUNCH_CHECK();

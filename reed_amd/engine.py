@@ -174,7 +174,7 @@ class Engine:
 
         sag = self.save_act_grad if self.save_act_grad is not None else M > self.SAVE_ACT_GRAD_MIN_TOKENS
         self._sag = sag   # (the projector forward of this call follows it)
-        tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, prec=prec, act_grad=sag) if need_grad else None
+        tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, t=t, prec=prec, act_grad=sag) if need_grad else None
         # epilogues of a layer whose saved array feeds the backward (gemm.h): derivative-saving forms when there is a backward
         epi_silu = EPI_SILU_G if need_grad and sag else EPI_SILU
         epi_gelu = EPI_GELU_G if need_grad and sag else EPI_GELU
@@ -383,10 +383,16 @@ class Engine:
         else:
             ops.gemm(NN, epi, dy, self.W(wname), Mtok, K, N, out, N, K, K, **kw)
 
-    def backward(self, tp, dout, dzs):
+    def backward(self, tp, dout, dzs, need_x=False, need_t=False, frozen=False):
+        """Parameter gradients into the gradient arena; returns (dL/dx f32 [B, C, HW, HW] | None, dL/dt f32 [B] | None), each
+        computed only when asked for (need_x / need_t).  frozen: no parameter requires grad — the activation-gradient chain alone
+        (the same launches in the same order: dx and dt have the bits of the full backward), no weight or bias gradient, no
+        gradient arena."""
         prec = getattr(self.m, "precision", "bf16")
         if getattr(tp, "prec", prec) != prec:
             raise RuntimeError("reed_amd.SiT: model.precision changed between forward and backward")
+        if frozen and self.reducer is not None:
+            raise RuntimeError(FROZEN_WITH_REDUCER)
         prev = ops.use(prec)
         prev_split = ops.f32_split(bool(getattr(self.m, "tf32", False))) if prec == "fp32" else None
         # gradient buckets are reduced beside this backward's GEMMs (RCCL channels hold CUs): only then does the library keep to
@@ -396,7 +402,7 @@ class Engine:
         if comm:
             ops.set_concurrent_comm(True)
         try:
-            return self._backward(tp, dout, dzs, ops.half_dtype(prec))
+            return self._backward(tp, dout, dzs, ops.half_dtype(prec), need_x, need_t, not frozen)
         finally:
             if comm:
                 ops.set_concurrent_comm(False)
@@ -404,7 +410,9 @@ class Engine:
                 ops.f32_split(prev_split)
             ops.use(prev)
 
-    def _backward(self, tp, dout, dzs, hdt):
+    def _backward(self, tp, dout, dzs, hdt, need_x, need_t, wgrads):
+        """wgrads = False (the frozen-weight backward): every launch that only feeds a parameter gradient is skipped; what is
+        left runs as it does with them."""
         m, L = self.m, self.L
         D, H, hd, Hm, T, P, C = self.D, self.H, self.hd, self.Hm, self.T, self.P, self.C
         B = tp.B
@@ -412,7 +420,8 @@ class Engine:
         dev = dout.device
         Nall = L.ada_rows
         hb = self._hb = hdt.itemsize
-        self.A.ensure_grad()
+        if wgrads:
+            self.A.ensure_grad()
         # the transposed copies of the blocks' weights (the dgrads' NT operand): built on first use, then kept fresh by the optimiser
         use_t = self.dgrad_nt if self.dgrad_nt is not None else (self.DGRAD_NT_MIN_TOKENS is not None and M >= self.DGRAD_NT_MIN_TOKENS)
         self._shadow_t = self.A.ensure_shadow_t(tp.prec) if (use_t and hb == 2) else None
@@ -426,7 +435,7 @@ class Engine:
         def f32(*s):
             return torch.empty(s, dtype=torch.float32, device=dev)
 
-        group_wgrad = ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
+        group_wgrad = wgrads and ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
         nws = ops.attention_bwd_ws_floats(B, T, H)       # delta = rowsum(dO * O) of the persistent attention backward
         attn_ws = f32(nws) if nws else None
         # the answer of the library ("this shape's dO GEMM has the head-dot epilogue") depends on which kernel the GEMM runs on:
@@ -438,7 +447,7 @@ class Engine:
                 ops.comm_forms())
         dot_delta = self._dot_delta if self.fused_delta and hdt != torch.float32 else {dkey: False}
         side = None
-        if self.wgrad_stream or (self.wgrad_stream is None and M <= self.wgrad_stream_max_tokens):
+        if wgrads and (self.wgrad_stream or (self.wgrad_stream is None and M <= self.wgrad_stream_max_tokens)):
             if self._side is None:
                 self._side = torch.cuda.Stream(device=dev)
             side = self._side
@@ -470,9 +479,10 @@ class Engine:
             return dy_, pg_
 
         pre = ln_bwd(dh, tp.x_last, tp.meanF, tp.rstdF, mf + hb * D, partF, self.depth - 1)
-        wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, C * P * P)), dev)
-        ops.smallk_wgrad(hbuf, False, dlin, wsf, self.G("final_layer.linear.weight"), None,
-                         self.G("final_layer.linear.bias"), M, D, self.NO, 1, acc)
+        if wgrads:
+            wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, C * P * P)), dev)
+            ops.smallk_wgrad(hbuf, False, dlin, wsf, self.G("final_layer.linear.weight"), None,
+                             self.G("final_layer.linear.bias"), M, D, self.NO, 1, acc)
         dmod = bf(B, Nall)
         offF = self.depth * 6 * D
         ops.reduce_mod_parts([(partF.data_ptr(), 2 * D, offF), (partF.data_ptr() + 4 * D, 2 * D, offF + D)], dmod, Nall,
@@ -481,8 +491,8 @@ class Engine:
         # With a reducer attached the adaLN weight gradient is computed block by block (rows of block i right after
         # block i's backward: dW_ada[i] = dmod[:, i]^T silu(c), a K = b GEMM) instead of one GEMM at the end, so each
         # slice's all-reduce overlaps the rest of backward; the arithmetic per output element is the same.
-        split_ada = self.reducer is not None if self.split_ada_wgrad is None else self.split_ada_wgrad
-        gp = self.A.grad.data_ptr()
+        split_ada = wgrads and (self.reducer is not None if self.split_ada_wgrad is None else self.split_ada_wgrad)
+        gp = self.A.grad.data_ptr() if wgrads else None
         dmp = dmod.data_ptr()
         # Factor path (a reducer that is reducing THIS backward, no gradient accumulation in flight): the adaLN weight
         # gradient contracts over the local batch only, so instead of all-reducing the [Nall, D] fp32 matrix (a third of
@@ -532,7 +542,7 @@ class Engine:
         for i in reversed(range(self.depth)):
             for j, dj in pending.items():
                 if dj == i + 1 and j in tp.proj:
-                    self._projector_bwd(j, tp, dz_by_proj.get(j), dx, B, acc, dev)
+                    self._projector_bwd(j, tp, dz_by_proj.get(j), dx, B, acc, dev, wgrads)
                     proj_left -= 1
                     if proj_left == 0 and self.reducer is not None:
                         self.reducer.ready("projectors")
@@ -549,13 +559,13 @@ class Engine:
             wg = [] if group_wgrad else None   # the block's four weight gradients: one launch at the end of the block
             if wg is not None:
                 wg.append((dy2, bk.u, b + "mlp.fc2.weight", D, Hm))
-            else:
+            elif wgrads:
                 self._wgrad(dy2, bk.u, b + "mlp.fc2.weight", M, D, Hm, acc, dev, side=side)
             da1 = bf(M, Hm)
             self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
             if wg is not None:
                 wg.append((da1, bk.h2, b + "mlp.fc1.weight", Hm, D))
-            else:
+            elif wgrads:
                 self._wgrad(da1, bk.h2, b + "mlp.fc1.weight", M, Hm, D, acc, dev, side=side)
             # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
             dh2 = dy2 if side is None and wg is None else bf(M, D)
@@ -567,7 +577,7 @@ class Engine:
                                      dy1, pg1, None, M, D, T)
             if wg is not None:
                 wg.append((dy1, bk.o, b + "attn.proj.weight", D, D))
-            else:
+            elif wgrads:
                 self._wgrad(dy1, bk.o, b + "attn.proj.weight", M, D, D, acc, dev, side=side)
             do = bf(M, D)
             dqkv = bf(M, 3 * D)
@@ -590,13 +600,14 @@ class Engine:
                 dpre = bf(M, 3 * D)
                 ops.qk_norm_bwd(dqkv, bk.qkv, bk.qstats, self.Wf(b + "attn.q_norm.weight"),
                                 self.Wf(b + "attn.k_norm.weight"), dpre, part, M, H, hd)
-                ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, acc,
-                               ws=self.ws((nb + 63) // 64 * 4 * hd, dev))
+                if wgrads:
+                    ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, acc,
+                                   ws=self.ws((nb + 63) // 64 * 4 * hd, dev))
                 dqkv = dpre
             if wg is not None:
                 wg.append((dqkv, bk.h, b + "attn.qkv.weight", 3 * D, D))
                 self._wgrad_block(wg, M, acc, dev, side)
-            else:
+            elif wgrads:
                 self._wgrad(dqkv, bk.h, b + "attn.qkv.weight", M, 3 * D, D, acc, dev, side=side)
             dh1 = do  # reuse
             self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)
@@ -630,7 +641,7 @@ class Engine:
                 c0, rows = ada_rows(i)
                 ops.gemm(TN, EPI_F32, g_recv.data_ptr() + hb * W * B * c0, s_all, rows, D, W * B,
                          gp + 4 * (L.ada_w_off + c0 * D), rows, D, D, dbias=gp + 4 * (L.ada_b_off + c0), accumulate=False)
-        elif not split_ada:
+        elif wgrads and not split_ada:
             ops.gemm(TN, EPI_F32, dmod, tp.silu_c, Nall, D, B, gp + 4 * L.ada_w_off, Nall, D, D,
                      dbias=gp + 4 * L.ada_b_off, accumulate=acc)
         ksteps = Nall // 64
@@ -644,23 +655,27 @@ class Engine:
         ops.reduce_slabs(wsd, slab, eff, dsilu, slab, False)
         # -- conditioning: label table + timestep MLP
         dtemb = bf(B, D)
-        gt = self.A.view(self.A.grad, "y_embedder.embedding_table.weight")
-        if not acc:
-            gt.zero_()
+        gt = None   # a frozen table: no scatter
+        if wgrads:
+            gt = self.A.view(self.A.grad, "y_embedder.embedding_table.weight")
+            if not acc:
+                gt.zero_()
         ops.label_cond_bwd(dsilu, tp.c, tp.labels_eff, dtemb, gt, B, D)
-        ops.linear_wgrad(dtemb, tp.t1, self.G("t_embedder.mlp.2.weight"), dbias=self.G("t_embedder.mlp.2.bias"),
-                         accumulate=acc, Mtok=B, N=D, K=D)
+        if wgrads:
+            ops.linear_wgrad(dtemb, tp.t1, self.G("t_embedder.mlp.2.weight"), dbias=self.G("t_embedder.mlp.2.bias"),
+                             accumulate=acc, Mtok=B, N=D, K=D)
         dt1 = bf(B, D)
         ops.gemm(NN, EPI_MUL if tp.act_grad else EPI_DSILU, dtemb, self.W("t_embedder.mlp.2.weight"), B, D, D, dt1, D, D, D, R=tp.t1p, ldr=D)
-        ops.linear_wgrad(dt1, tp.sin, self.G("t_embedder.mlp.0.weight"), dbias=self.G("t_embedder.mlp.0.bias"),
-                         accumulate=acc, Mtok=B, N=D, K=256)
-        # -- patch embed: dW[d,k] = sum_tokens bf16(dx)[token,d] * patch[token,k]
-        K = C * P * P
-        xb = bf(M, K)
-        ops.patchify_bf16(tp.x, xb, B, C, tp.x.shape[-1], P, 0)
-        wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, K)), dev)
-        ops.smallk_wgrad(dx, True, xb, wsf, self.G("x_embedder.proj.weight"), self.G("x_embedder.proj.bias"), None, M, D,
-                         K, 0, acc)
+        if wgrads:
+            ops.linear_wgrad(dt1, tp.sin, self.G("t_embedder.mlp.0.weight"), dbias=self.G("t_embedder.mlp.0.bias"),
+                             accumulate=acc, Mtok=B, N=D, K=256)
+            # -- patch embed: dW[d,k] = sum_tokens bf16(dx)[token,d] * patch[token,k]
+            K = C * P * P
+            xb = bf(M, K)
+            ops.patchify_bf16(tp.x, xb, B, C, tp.x.shape[-1], P, 0)
+            wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, K)), dev)
+            ops.smallk_wgrad(dx, True, xb, wsf, self.G("x_embedder.proj.weight"), self.G("x_embedder.proj.bias"), None, M, D,
+                             K, 0, acc)
         if self.reducer is not None:
             if fg:   # adaLN weights and biases are global-batch averages already: reduce only the embedders' part
                 eb, ee = self.reducer.buckets["embed"]
@@ -670,19 +685,32 @@ class Engine:
                     for i in reversed(range(self.depth + 1)):
                         self.reducer.ready(f"ada{i}")
                 self.reducer.ready("embed")
+        # -- the inputs' gradients, after everything they depend on: dL/dt through the sinusoid from dsin = dt1 @ W0 (fp32 out: not
+        # rounded again), dL/dx = the convolution's input gradient of the finished token gradient
+        dt_in = dx_in = None
+        if need_t:
+            dsin = f32(B, 256)
+            ops.gemm(NN, EPI_F32, dt1, self.W("t_embedder.mlp.0.weight"), B, 256, D, dsin, D, 256, 256)
+            dt_in = f32(B)
+            ops.timestep_sinusoid_bwd(tp.t, dsin, dt_in, B)
+        if need_x:
+            dx_in = torch.empty_like(tp.x)
+            ops.patch_embed_bwd_x(dx, self.W("x_embedder.proj.weight"), dx_in, B, C, tp.x.shape[-1], P, D)
         if side is not None:  # the optimiser / next micro-step (same stream as this backward) sees every weight gradient
             torch.cuda.current_stream().wait_stream(side)
-        self.grad_live = True
-        self._attach_grads()
+        if wgrads:
+            self.grad_live = True
+            self._attach_grads()
+        return dx_in, dt_in
 
-    def _projector_bwd(self, j, tp, dz, dx, B, acc, dev):
+    def _projector_bwd(self, j, tp, dz, dx, B, acc, dev, wgrads=True):
         m, D, T = self.m, self.D, self.T
         Pd, Z = m.projector_dim, m.z_dims[j]
         pj = tp.proj[j]
         R = pj.R
         pre = f"projectors.{j}."
         if dz is None:  # projector output unused by the loss: zero grads (torch would leave them None)
-            if not acc:
+            if wgrads and not acc:
                 b, e = self.L.range_of(pre)
                 self.A.grad[b:e].zero_()
             return
@@ -692,14 +720,17 @@ class Engine:
             dz = dz.to(hdt)
         dz = dz.contiguous()
         bf = lambda *s: torch.empty(s, dtype=hdt, device=dev)  # noqa: E731
-        self._wgrad(dz, pj.p2, pre + "4.weight", R, Z, Pd, acc, dev)
+        if wgrads:
+            self._wgrad(dz, pj.p2, pre + "4.weight", R, Z, Pd, acc, dev)
         d2 = bf(R, Pd)
         epi_dsilu = EPI_MUL if tp.act_grad else EPI_DSILU
         ops.gemm(NN, epi_dsilu, dz, self.W(pre + "4.weight"), R, Pd, Z, d2, Z, Pd, Pd, R=pj.p2p, ldr=Pd)
-        self._wgrad(d2, pj.p1, pre + "2.weight", R, Pd, Pd, acc, dev)
+        if wgrads:
+            self._wgrad(d2, pj.p1, pre + "2.weight", R, Pd, Pd, acc, dev)
         d1 = bf(R, Pd)
         ops.gemm(NN, epi_dsilu, d2, self.W(pre + "2.weight"), R, Pd, Pd, d1, Pd, Pd, Pd, R=pj.p1p, ldr=Pd)
-        self._wgrad(d1, pj.xin, pre + "0.weight", R, Pd, D, acc, dev)
+        if wgrads:
+            self._wgrad(d1, pj.xin, pre + "0.weight", R, Pd, D, acc, dev)
         if m.z_types[j] == "i":
             ops.gemm(NN, EPI_ADDF32_RB, d1, self.W(pre + "0.weight"), R, D, Pd, dx, Pd, D, D)
         else:
@@ -708,12 +739,19 @@ class Engine:
             ops.token_mean_bwd(dmean, dx, B, T, D)
         tp.proj[j] = None
 
+    def _params(self):
+        if self._named is None:   # named_parameters() walks the module tree (1 ms per call on SiT-XL/2): once
+            self._named = [(name, p) for name, p in self.m.named_parameters()]
+        return self._named
+
+    def any_trainable(self):
+        """Whether any parameter requires grad (pos_embed never does): read afresh from the cached parameter list."""
+        return any(p.requires_grad for _, p in self._params())
+
     def _attach_grads(self):
         """Expose the grad arena through param.grad (views), for torch.optim / clip_grad_norm_ compatibility."""
         g = self.A.grad
-        if self._named is None:   # named_parameters() walks the module tree (1 ms per call on SiT-XL/2): once
-            self._named = [(name, p) for name, p in self.m.named_parameters()]
-        for name, p in self._named:
+        for name, p in self._params():
             if p.requires_grad and p.grad is None:
                 p.grad = self.A.view(g, name)
 
@@ -722,12 +760,20 @@ class Engine:
         self.grad_live = False
 
 
+FROZEN_WITH_REDUCER = ("reed_amd.SiT: an input requires grad while no parameter does (the frozen-weight backward), and a gradient "
+                       "reducer is attached to this model: the reducer waits for parameter gradients that backward never writes. "
+                       "Detach the reducer, or leave the parameters trainable.")
+
+
 class _SiTFunction(torch.autograd.Function):
+    """anchor: a one-element leaf that requires grad, so that a graph exists when only the parameters (arena views the Function
+    never sees as inputs) do; None in the frozen-weight mode, where x or t carries the graph."""
+
     @staticmethod
     def forward(ctx, anchor, model, x, t, y, inference, drop):
         eng = model.engine()
         out, zs, tape = eng.forward(x, t, y, inference, True, drop)
-        ctx.eng, ctx.tape = eng, tape
+        ctx.eng, ctx.tape, ctx.frozen = eng, tape, anchor is None
         ctx.nz = 0 if zs is None else len(zs)
         ctx.set_materialize_grads(False)
         return (out,) + (tuple(zs) if zs else ())
@@ -740,16 +786,21 @@ class _SiTFunction(torch.autograd.Function):
         ctx.tape = None
         if dout is None:
             dout = torch.zeros_like(tape.x)
-        # the user may have dropped p.grad (zero_grad(set_to_none=True)) -> overwrite semantics
-        if eng._sentinel is None:
-            eng._sentinel = next(p for p in eng.m.parameters() if p.requires_grad)
-        if eng._sentinel.grad is None:
-            eng.grad_live = False
-        eng.backward(tape, dout, list(dzs) if ctx.nz else None)
-        return (None,) * 7
+        if not ctx.frozen:
+            # the user may have dropped p.grad (zero_grad(set_to_none=True)) -> overwrite semantics
+            if eng._sentinel is None:
+                eng._sentinel = next(p for p in eng.m.parameters() if p.requires_grad)
+            if eng._sentinel.grad is None:
+                eng.grad_live = False
+        need_x, need_t = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dx, dt = eng.backward(tape, dout, list(dzs) if ctx.nz else None, need_x, need_t, ctx.frozen)
+        return None, None, dx, dt, None, None, None
 
 
 def sit_apply(model, x, t, y, inference=True):
+    """Builds an autograd graph when gradients are enabled and the parameters are trainable, x.requires_grad or t.requires_grad;
+    x.grad / t.grad come back in the caller's dtype and shape (the casts below are torch's, in front of the Function).  With an
+    input that requires grad and NO trainable parameter the backward is the frozen-weight one (Engine.backward)."""
     ops.require_cuda(x, "x")
     eng = model.engine()
     drop = None
@@ -759,12 +810,24 @@ def sit_apply(model, x, t, y, inference=True):
         elif model.training:  # LabelEmbedder.token_drop (sit.py:84-93): device RNG draw
             drop = torch.rand(y.shape[0], device=y.device) < model.class_dropout_prob
     need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in (model.x_embedder.proj.weight,))
+    frozen = False
+    if torch.is_grad_enabled() and (x.requires_grad or t.requires_grad):
+        # the walk over every parameter only here: a partly frozen model computes all gradients, as it does without x.grad
+        need_grad, frozen = True, not eng.any_trainable()
+        if frozen and eng.reducer is not None:
+            raise RuntimeError(FROZEN_WITH_REDUCER)
+        if x.requires_grad and x.dtype != torch.float32:
+            x = x.float()
+        if t.requires_grad:
+            t = t.reshape(-1)
+            if t.dtype != torch.float32:
+                t = t.float()
     if not need_grad:
         out, zs, _ = eng.forward(x, t, y, inference, False, drop)
         return out, zs
-    if not hasattr(model, "_anchor") or model._anchor.device != x.device:
+    if not frozen and (not hasattr(model, "_anchor") or model._anchor.device != x.device):
         model._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-    res = _SiTFunction.apply(model._anchor, model, x, t, y, inference, drop)
+    res = _SiTFunction.apply(None if frozen else model._anchor, model, x, t, y, inference, drop)
     out, zs = res[0], (list(res[1:]) if len(res) > 1 else None)
     if inference:
         zs = None

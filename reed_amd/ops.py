@@ -574,6 +574,12 @@ def patch_embed_fwd(x, w, bias, pos, tokens, B, C, HW, P, D):
     _call("reed_patch_embed_fwd", _p(x), _p(w), _p(bias), _p(pos), _p(tokens), B, C, HW, P, D, _stream())
 
 
+def patch_embed_bwd_x(dtok, w, dx, B, C, HW, P, D):
+    """dx f32 [B, C, HW, HW] = the patch-embed convolution's input gradient from the f32 token gradient dtok [B T, D] (rounded to
+    the operand type on load) and the operand-type weight w [D, C P P]; every element written once."""
+    _call("reed_patch_embed_bwd_x", _p(dtok), _p(w), _p(dx), B, C, HW, P, D, _stream())
+
+
 def patchify_bf16(x, out, B, C, HW, P, order):
     _call("reed_patchify_bf16", _p(x), _p(out), B, C, HW, P, order, _stream())
 
@@ -589,6 +595,11 @@ def smallk_wgrad(wide, wide_is_f32, small, ws, out, colsum_wide, colsum_small, M
 
 def timestep_sinusoid(t, out, B, dim=256, max_period=10000.0):
     _call("reed_timestep_sinusoid", _p(t), _p(out), B, dim, max_period, _stream())
+
+
+def timestep_sinusoid_bwd(t, dsin, dt, B, dim=256, max_period=10000.0):
+    """dt f32 [B] from dsin f32 [B, dim], the gradient with respect to timestep_sinusoid's table."""
+    _call("reed_timestep_sinusoid_bwd", _p(t), _p(dsin), _p(dt), B, dim, max_period, _stream())
 
 
 def label_cond(labels, drop, num_classes, table, t_emb, labels_out, c, silu_c, B, D, table_rows=None, err=None):
