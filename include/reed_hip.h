@@ -105,6 +105,29 @@ int reed_gemm_f32_split(int on);
 int reed_gemm_plan(int layout, int epilogue, int M, int N, int K, int split_k, int flags, int rows_per_gate, int ncu,
                    int forced_tile, int colsplit, int use288, int concurrent_comm, int* launches);
 
+/* ---------------------------------------------------------------------------------------------
+ * MX-fp8 block GEMMs (sampling only; no counterpart in the reference).  Format: OCP e4m3fn elements (bias 7, max 448, NaN 0x7F /
+ * 0xFF), blocks of 32 consecutive k, one E8M0 scale byte per block (value 2^(byte - 127)).  Finite block, amax > 0:
+ * X = clamp(floor(log2 amax) - 8, -127, 127), byte = X + 127, code = x 2^-X rounded to nearest-even onto the e4m3 grid, signs and
+ * subnormals kept, saturated to +-448.  amax = 0: byte 127 and signed zeros.  A block holding an inf or a NaN: byte 0xFF and
+ * every code 0x7F; every output that consumes it is NaN.  The fp32-operand library answers all three entries with 1001.
+ *
+ * reed_mx_quantize: x 16-bit [R, K] (row stride ldx elements) -> codes u8 [R, K] (row stride ldq bytes), scales u8 [R, K/32] (row
+ * stride lds bytes).  K % 32 == 0, ldx and ldq multiples of 8, x 16-byte and codes 8-byte aligned.  Writes live elements only.
+ * reed_gemm_mxfp8: C[M,N] = epilogue(sum_blocks 2^(Xa + Xw) sum_k a w + bias), fp32 accumulation, NT: Aq [M,K] / Wq [N,K] codes
+ * (row strides lda / ldw bytes, multiples of 16) with their scales As [M,K/32] / Ws [N,K/32] (row strides multiples of 4 bytes).
+ * Epilogues 0 (bf16), 1 (GELU) and 3 (gate + residual) with reed_gemm's arguments and rounding points.  K % 128 == 0,
+ * N % 128 == 0, any M >= 1.
+ * reed_gemm_mxfp8_plan: host arithmetic, no device call: 0 where reed_gemm_mxfp8 takes (epilogue, M, N, K), else 1001.
+ * ------------------------------------------------------------------------------------------- */
+int reed_mx_quantize(const void* x, int64_t ldx, void* codes, int64_t ldq, void* scales, int64_t lds, int R, int K,
+                     void* stream);
+int reed_gemm_mxfp8(int epilogue, const void* Aq, int64_t lda, const void* As, int64_t ldas, const void* Wq, int64_t ldw,
+                    const void* Ws, int64_t ldws, int M, int N, int K, void* C, int64_t ldc, void* C2, int64_t ldc2,
+                    const void* R, int64_t ldr, const void* bias, const void* gate, int64_t ldgate, int rows_per_gate,
+                    void* stream);
+int reed_gemm_mxfp8_plan(int epilogue, int M, int N, int K);
+
 /* bias gradient: out[n] (+)= sum_m x[m,n], x bf16 [M,N] (row stride ld); ws: caller scratch of
  * reed_colsum_ws_floats(M, N) floats. Deterministic (fixed reduction order). */
 int64_t reed_colsum_ws_floats(int M, int N);

@@ -152,6 +152,9 @@ class ParamArena:
         self.shadow_gen = 0        # bumped whenever the shadow changes (a cast of the master; an optimiser step)
         self.shadow_t_gen = -1
         self.pending_t = None      # event behind the optimiser's transposes
+        # MX-fp8 copies of the blocks' linear weights (ensure_mx): the fp8 sampling path's GEMM operands
+        self.mx_codes = self.mx_scales = self.mx_seg = self.mx_dtype = None
+        self.mx_gen = -1
 
     def wait(self, name):
         """Order the current stream after the optimiser's update of bucket `name` (no-op when none is in flight)."""
@@ -209,6 +212,39 @@ class ParamArena:
             name = f"blocks.{i}.{w}.weight"
             toff, n_out, k_in = self.t_seg[name]
             ops.transpose_bf16(self.shadow.data_ptr() + es * self.layout.off(name), self.shadow_t.data_ptr() + es * toff, n_out, k_in)
+
+    def ensure_mx(self, precision="bf16"):
+        """MX-fp8 copies of the blocks' four linear weights for the fp8 sampling path (csrc/gemm_mxfp8.hip): e4m3 codes [n_out, k_in]
+        and E8M0 scale bytes [n_out, k_in / 32] per weight, quantised from the 16-bit shadow (which the caller has ensured) —
+        17/32 of a byte per parameter, 0.46 GB for XL/2.  Built on first use, rebuilt whenever the shadow moved (shadow_gen: a
+        cast of the master after load_state_dict or a precision change, an optimiser step); nothing else writes them.  Weights
+        whose k_in is not a multiple of 32 have no copy.  Returns {name: (codes address, scales address)}."""
+        from . import ops
+        if self.shadow.element_size() != 2:
+            raise RuntimeError("reed_amd: the MX-fp8 weights are quantised from a 16-bit shadow (precision bf16 / fp16)")
+        if self.mx_seg is None:
+            self.mx_seg, qoff, soff = {}, 0, 0
+            for name in self.t_names():
+                n_out, k_in = (int(v) for v in self.layout.seg[name][1])
+                if k_in % ops.MX_BLOCK == 0:
+                    self.mx_seg[name] = (qoff, soff, n_out, k_in)
+                    qoff += n_out * k_in
+                    soff += _align(n_out * (k_in // ops.MX_BLOCK), 16)
+            self.mx_codes = torch.empty(qoff, dtype=torch.uint8, device=self.device)
+            self.mx_scales = torch.empty(soff, dtype=torch.uint8, device=self.device)
+            self.mx_gen = -1
+        if self.mx_gen != self.shadow_gen or self.mx_dtype != self.shadow.dtype:
+            self.wait_all()
+            prev = ops.use(precision)
+            try:
+                for name, (qoff, soff, n_out, k_in) in self.mx_seg.items():
+                    ops.mx_quantize(self.shadow.data_ptr() + 2 * self.layout.off(name), self.mx_codes.data_ptr() + qoff,
+                                    self.mx_scales.data_ptr() + soff, n_out, k_in)
+            finally:
+                ops.use(prev)
+            self.mx_gen, self.mx_dtype = self.shadow_gen, self.shadow.dtype
+        cp, sp = self.mx_codes.data_ptr(), self.mx_scales.data_ptr()
+        return {name: (cp + q, sp + s) for name, (q, s, _, _) in self.mx_seg.items()}
 
     def ensure_shadow_t(self, precision="bf16"):
         """The transposed copies, as fresh as the shadow (which the caller has ensured): allocate on first use; rebuild everything

@@ -413,3 +413,29 @@ extern "C" int reed_gemm_plan(int layout, int epilogue, int M, int N, int K, int
   return plan.n;
 }
 #endif
+
+// Where the MX-fp8 block GEMM (gemm_mxfp8.hip: 128 x 128 tiles, a 128-code K step) applies: the three epilogues of the inference
+// forward's block linears, whole column tiles and K steps, ragged rows.  The fp32-operand build has no such kernel: every
+// entry of the family answers with the argument error there.
+extern "C" int reed_gemm_mxfp8_plan(int epilogue, int M, int N, int K) {
+#if defined(REED_FP32)
+  (void)M; (void)N; (void)K;
+  REED_CHECK_ARG(false, "reed_gemm_mxfp8: epilogue %d: not part of the fp32-operand build (use the bf16 / fp16 library)", epilogue);
+#else
+  REED_CHECK_ARG(epi_in(epi_set(EPI_BF16, EPI_GELU, EPI_GATE_RES), epilogue), "reed_gemm_mxfp8: epilogue %d: 0, 1 or 3", epilogue);
+  REED_CHECK_ARG(M >= 1 && N >= 128 && N % 128 == 0 && K >= 128 && K % 128 == 0,
+                 "reed_gemm_mxfp8: M=%d >= 1, N=%d and K=%d positive multiples of 128", M, N, K);
+#endif
+  return REED_OK;
+}
+#if defined(REED_FP32)
+extern "C" int reed_mx_quantize(const void*, int64_t, void*, int64_t, void*, int64_t, int, int, void*) {
+  REED_CHECK_ARG(false, "reed_mx_quantize: not part of the fp32-operand build (use the bf16 / fp16 library)");
+  return REED_OK;
+}
+extern "C" int reed_gemm_mxfp8(int epilogue, const void*, int64_t, const void*, int64_t, const void*, int64_t, const void*, int64_t,
+                               int M, int N, int K, void*, int64_t, void*, int64_t, const void*, int64_t, const void*, const void*,
+                               int64_t, int, void*) {
+  return reed_gemm_mxfp8_plan(epilogue, M, N, K);
+}
+#endif

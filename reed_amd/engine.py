@@ -11,6 +11,7 @@ Per block the launch sequence is
 and the modulation of ALL blocks is one GEMM forward (silu(c) @ W_ada_all^T) and two backward.
 """
 import contextlib
+import logging
 import os
 import types
 
@@ -20,6 +21,7 @@ from . import ops
 from .ops import (NT, NN, TN, EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB,
                   EPI_GELU_G, EPI_SILU_G, EPI_MUL)
 
+logger = logging.getLogger(__name__)
 
 class Engine:
     # Kernel forms picked by the token count per GPU (both measured on MI355X with SiT-XL/2; bench.py prints them under
@@ -89,6 +91,7 @@ class Engine:
         # the attention backward's delta = rowsum(dO * O) from the epilogue of the GEMM that produces dO (False: the row kernel;
         # tests/test_model_gpu.py::test_bench_plan_matches_the_golden_pinned_plan_at_b256 compares the two)
         self.fused_delta = True
+        self._fp8_logged = False  # the list of fp8 / 16-bit layers has been logged
         self._err = None         # sticky device flag: a label outside the embedding table was seen (see check_errors)
 
     def _check_dims(self, prec):
@@ -139,8 +142,25 @@ class Engine:
         return self._ws_side
 
     # ---- forward -------------------------------------------------------------------
+    FP8_LAYERS = ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")
+
+    def fp8_layers(self, tokens=None, precision=None):
+        """{block linear: True where it runs on the MX-fp8 GEMM with SiT.fp8 set, False where it stays 16-bit} for a forward of
+        `tokens` rows (default: one sample) — what reed_gemm_mxfp8_plan says of each layer's (epilogue, M, N, K), host arithmetic."""
+        D, Hm = self.D, self.Hm
+        M = int(tokens) if tokens else self.T
+        prec = precision or getattr(self.m, "precision", "bf16")
+        if prec not in ("bf16", "fp16"):
+            return {n: False for n in self.FP8_LAYERS}
+        shapes = {"attn.qkv": (EPI_BF16, 3 * D, D), "attn.proj": (EPI_GATE_RES, D, D), "mlp.fc1": (EPI_GELU, Hm, D),
+                  "mlp.fc2": (EPI_GATE_RES, D, Hm)}
+        return {n: ops.gemm_mxfp8_plan(e, M, N, K, precision=prec) for n, (e, N, K) in shapes.items()}
+
     def forward(self, x, t, y, inference, need_grad, drop):
         prec = getattr(self.m, "precision", "bf16")
+        if need_grad and getattr(self.m, "fp8", False):
+            raise RuntimeError("reed_amd.SiT: fp8 is a sampling mode (inference forward under torch.no_grad()); a forward that "
+                               "builds a graph (training, input gradients) needs model.fp8 = False")
         with ops.build(prec, bool(getattr(self.m, "tf32", False))):
             return self._forward(x, t, y, inference, need_grad, drop, prec)
 
@@ -219,6 +239,27 @@ class Engine:
         if not need_grad:  # inference: ping-pong buffers, nothing saved
             xa, xb = tok, f32(M, D)
             h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
+        # fp8 sampling (SiT.fp8; inference branch, 16-bit builds): the block linears that reed_gemm_mxfp8 takes at this token count run
+        # on MX-fp8 operands — the activation quantised by a row pass in front of the GEMM, the weight from the arena's quantised
+        # copy — each layer decided on its own; everything else, and every other layer, stays on the 16-bit kernels.
+        mx_on = ()
+        if not need_grad and prec in ("bf16", "fp16") and getattr(m, "fp8", False):
+            layers = self.fp8_layers(M, prec)
+            mx_on = frozenset(n for n, on in layers.items() if on)
+            if not self._fp8_logged:
+                self._fp8_logged = True
+                logger.info("fp8 sampling: MX-fp8 block GEMMs for %s; 16-bit for %s", sorted(mx_on) or "no layer",
+                            sorted(n for n, on in layers.items() if not on) or "no layer")
+        if mx_on:
+            mxw = self.A.ensure_mx(prec)
+            kmax = max(D, Hm)
+            aq = torch.empty((M, kmax), dtype=torch.uint8, device=dev)
+            asc = torch.empty((M, kmax // ops.MX_BLOCK), dtype=torch.uint8, device=dev)
+
+            def mx_gemm(name, epi, act, N, K, C, ldc, **kw):
+                wq, wsc = mxw[name + ".weight"]
+                ops.mx_quantize(act, aq, asc, M, K)
+                ops.gemm_mxfp8(epi, aq, asc, wq, wsc, M, N, K, C, ldc, bias=self.W(name + ".bias"), **kw)
         xcur = tok
         zs_by_proj = {}
         for i in range(self.depth):
@@ -243,8 +284,11 @@ class Engine:
                 xmid = xb if xcur is xa else xa
                 xout = xcur  # safe: fc2's epilogue reads R=xmid, writes xout; xcur is dead after proj
             ops.ln_modulate_fwd(xcur, mb, mb + hb * D, Nall, h, mean1, rstd1, M, D, T)
-            ops.gemm(NT, EPI_BF16, h, self.W(b + "attn.qkv.weight"), M, 3 * D, D, qkv, D, D, 3 * D,
-                     bias=self.W(b + "attn.qkv.bias"))
+            if "attn.qkv" in mx_on:
+                mx_gemm(b + "attn.qkv", EPI_BF16, h, 3 * D, D, qkv, 3 * D)
+            else:
+                ops.gemm(NT, EPI_BF16, h, self.W(b + "attn.qkv.weight"), M, 3 * D, D, qkv, D, D, 3 * D,
+                         bias=self.W(b + "attn.qkv.bias"))
             qkv_a, qstats = qkv, None
             if m.qk_norm:
                 qkv_a = bf(M, 3 * D)
@@ -252,13 +296,22 @@ class Engine:
                 ops.qk_norm_fwd(qkv, self.Wf(b + "attn.q_norm.weight"), self.Wf(b + "attn.q_norm.bias"),
                                 self.Wf(b + "attn.k_norm.weight"), self.Wf(b + "attn.k_norm.bias"), qkv_a, qstats, M, H, hd)
             ops.attention_fwd(qkv_a, o, lse, B, T, H, hd)
-            ops.gemm(NT, EPI_GATE_RES, o, self.W(b + "attn.proj.weight"), M, D, D, xmid, D, D, D, C2=y1, ldc2=D,
-                     R=xcur, ldr=D, bias=self.W(b + "attn.proj.bias"), gate=mb + 2 * hb * D, ldgate=Nall, rows_per_gate=T)
+            if "attn.proj" in mx_on:
+                mx_gemm(b + "attn.proj", EPI_GATE_RES, o, D, D, xmid, D, R=xcur, ldr=D, gate=mb + 2 * hb * D, ldgate=Nall, rows_per_gate=T)
+            else:
+                ops.gemm(NT, EPI_GATE_RES, o, self.W(b + "attn.proj.weight"), M, D, D, xmid, D, D, D, C2=y1, ldc2=D,
+                         R=xcur, ldr=D, bias=self.W(b + "attn.proj.bias"), gate=mb + 2 * hb * D, ldgate=Nall, rows_per_gate=T)
             ops.ln_modulate_fwd(xmid, mb + 3 * hb * D, mb + 4 * hb * D, Nall, h2, mean2, rstd2, M, D, T)
-            ops.gemm(NT, epi_gelu, h2, self.W(b + "mlp.fc1.weight"), M, Hm, D, a1, D, D, Hm, C2=u, ldc2=Hm,
-                     bias=self.W(b + "mlp.fc1.bias"))
-            ops.gemm(NT, EPI_GATE_RES, u, self.W(b + "mlp.fc2.weight"), M, D, Hm, xout, Hm, Hm, D, C2=y2, ldc2=D,
-                     R=xmid, ldr=D, bias=self.W(b + "mlp.fc2.bias"), gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
+            if "mlp.fc1" in mx_on:
+                mx_gemm(b + "mlp.fc1", EPI_GELU, h2, Hm, D, None, 0, C2=u, ldc2=Hm)
+            else:
+                ops.gemm(NT, epi_gelu, h2, self.W(b + "mlp.fc1.weight"), M, Hm, D, a1, D, D, Hm, C2=u, ldc2=Hm,
+                         bias=self.W(b + "mlp.fc1.bias"))
+            if "mlp.fc2" in mx_on:
+                mx_gemm(b + "mlp.fc2", EPI_GATE_RES, u, D, Hm, xout, D, R=xmid, ldr=D, gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
+            else:
+                ops.gemm(NT, EPI_GATE_RES, u, self.W(b + "mlp.fc2.weight"), M, D, Hm, xout, Hm, Hm, D, C2=y2, ldc2=D,
+                         R=xmid, ldr=D, bias=self.W(b + "mlp.fc2.bias"), gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
             if need_grad:
                 tp.blocks.append(types.SimpleNamespace(x=xcur, mean1=mean1, rstd1=rstd1, h=h, qkv=qkv, qkv_a=qkv_a,
                                                        qstats=qstats, o=o, lse=lse,

@@ -59,6 +59,11 @@ def folder_name(args):
     return name
 
 
+# what --sample-precision fp8 costs and buys, as measured (profiles/mxfp8_sampling.txt)
+FP8_HELP = ("one SiT-XL/2 evaluation lands 2.0e-2 (relative L2) from fp32 where fp16 / bf16 land 4.6e-3, cosine 0.9998; "
+            "NOT a speed mode yet: with the present kernel an evaluation at batch 64 takes 20.2 ms against 18.4 ms in fp16 (0.91x)")
+
+
 def build_parser():
     from .models.sit import SiT_models
     parser = argparse.ArgumentParser()
@@ -95,12 +100,13 @@ def build_parser():
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft-{ema,mse} checkpoint (diffusers directory or its diffusion_pytorch_model file): "
                              "decode with the in-repo decoder instead of the diffusers package")
-    parser.add_argument("--sample-precision", type=str, choices=["fp16", "bf16", "fp32", "tf32"], default=None,
+    parser.add_argument("--sample-precision", type=str, choices=["fp16", "bf16", "fp32", "tf32", "fp8"], default=None,
                         help="operand type of the model evaluations: fp16 = 10-bit mantissa (the reference's TF32; the default "
                              "with --tf32), fp32 = the reference's --no-tf32 arithmetic (the default with --no-tf32), bf16 = the "
                              "training precision, tf32 = fp32 operands and range with every GEMM product taken as three bf16 MFMA "
                              "products (closer to fp32 than TF32; no half-precision overflow, so no re-sampling fallback), for the "
-                             "model and the VAE decoder alike")
+                             "model and the VAE decoder alike; fp8 = fp16 with the transformer blocks' four linears as MX-fp8 block "
+                             "GEMMs (OCP e4m3, one power-of-two scale per 32 elements; VAE decode in fp16): " + FP8_HELP)
     return parser
 
 
@@ -134,7 +140,9 @@ def finite_or_retry(sampler, kw, model):
     """Run one batch.  IEEE half saturates at 65504 where bf16 and the reference's TF32 do not: a checkpoint with large
     activation outliers would give inf / nan latents silently.  One isfinite reduction per batch (one host
     sync per several hundred model evaluations); a non-finite fp16 batch is re-sampled once with bf16 operands from the same
-    latents, labels and device RNG state (the SDE sampler draws noise per step), and anything still non-finite raises."""
+    latents, labels and device RNG state (the SDE sampler draws noise per step), and anything still non-finite raises.  Under
+    --sample-precision fp8 (model.fp8, which stays set) the retry is bf16 activations with the same MX-fp8 block GEMMs: a block that
+    holds an inf or a NaN quantises to NaN, never to a clamped finite value, so the overflow of an fp16 activation is still seen."""
     dev = kw["latents"].device
     rng = torch.cuda.get_rng_state(dev)
     samples = sampler(**kw).to(torch.float32)
@@ -192,7 +200,9 @@ def main(args):
     model.load_state_dict(state_dict, strict=False)
     model.eval()
     from . import ops
-    model.precision, model.tf32 = ops.build_of(sample_precision(args))   # "tf32" = the fp32 build with the split GEMM
+    prec = sample_precision(args)
+    model.fp8 = prec == "fp8"                                           # "fp8" = the fp16 build with the blocks' linears in MX-fp8
+    model.precision, model.tf32 = ops.build_of("fp16" if model.fp8 else prec)   # "tf32" = the fp32 build with the split GEMM
     assert args.cfg_scale >= 1.0, "In almost all cases, cfg_scale be >= 1.0"
     if args.cfg_scale > 1.0:
         assert args.num_classes == 1000, "the samplers hard-code the null class id 1000 (samplers.py:59)"

@@ -100,6 +100,10 @@ class SiT(nn.Module):
         # at precision "fp32" only: every fp32 GEMM product as three bf16 MFMA products (ops.f32_split: --allow-tf32 /
         # --sample-precision tf32); the engine applies it beside ops.use("fp32") and restores it.  The attention stays exact fp32.
         self.tf32 = False
+        # at precision "bf16" / "fp16" only, inference forwards only: the blocks' four linears (qkv, proj, fc1, fc2) as MX-fp8 block
+        # GEMMs (csrc/gemm_mxfp8.hip: e4m3 codes, one power-of-two scale per 32 k) wherever the kernel takes the layer's shape
+        # (Engine.fp8_layers()); generate.py --sample-precision fp8.  A forward that builds a graph raises while it is set.
+        self.fp8 = False
 
     # ------------------------------------------------------------------ structure
     def _param_shapes(self):
@@ -278,7 +282,13 @@ class SiT(nn.Module):
 
     def load_state_dict(self, *args, **kwargs):
         self._arena.wait_all()
-        return super().load_state_dict(*args, **kwargs)
+        res = super().load_state_dict(*args, **kwargs)
+        # the 16-bit shadow (and what is derived from it: transposed and MX-fp8 copies) is re-cast at the next forward.  The version
+        # counter of the master does not say so by itself: once the arena has moved devices the parameters are rebound through
+        # `.data` (_rebind) and a copy into them leaves the master's counter alone — a model that had already run kept evaluating
+        # its old 16-bit weights after load_state_dict.
+        self._arena.shadow_version = -1
+        return res
 
     def engine(self):
         if self._engine is None:

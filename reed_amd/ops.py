@@ -406,6 +406,32 @@ def gemm_plan(lay, epi, M, N, K, split_k=1, *, dbias=False, slab=False, dot_oper
     return 0, launches
 
 
+# ---------------- MX-fp8 block GEMMs (sampling; csrc/gemm_mxfp8.hip) ----------------
+MX_BLOCK = 32   # elements along K that share one E8M0 scale byte
+
+
+def gemm_mxfp8_plan(epi, M, N, K, precision="bf16"):
+    """True where reed_gemm_mxfp8 takes (epi, M, N, K) (reed_gemm_mxfp8_plan: host arithmetic, runs without a GPU)."""
+    return _lib.load(precision).reed_gemm_mxfp8_plan(int(epi), int(M), int(N), int(K)) == 0
+
+
+def mx_quantize(x, codes, scales, R, K, ldx=None, ldq=None, lds=None):
+    """16-bit rows x [R, K] -> e4m3 codes u8 [R, K] and E8M0 scale bytes u8 [R, K / 32] (reed_mx_quantize; tensors or raw
+    device addresses, leading dimensions default to the row lengths)."""
+    _call("reed_mx_quantize", _p(x), K if ldx is None else ldx, _p(codes), K if ldq is None else ldq, _p(scales),
+          K // MX_BLOCK if lds is None else lds, R, K, _stream())
+
+
+def gemm_mxfp8(epi, Aq, As, Wq, Ws, M, N, K, C, ldc, lda=None, ldas=None, ldw=None, ldws=None, C2=None, ldc2=0, R=None, ldr=0,
+               bias=None, gate=None, ldgate=0, rows_per_gate=1):
+    """C = epilogue(Aq Wq^T with the block scales As / Ws + bias): reed_gemm_mxfp8, the NT GEMM of pre-quantised operands;
+    outputs, bias, gate and residual as for gemm() with the same epilogue."""
+    kb = K // MX_BLOCK
+    _call("reed_gemm_mxfp8", epi, _p(Aq), K if lda is None else lda, _p(As), kb if ldas is None else ldas, _p(Wq),
+          K if ldw is None else ldw, _p(Ws), kb if ldws is None else ldws, M, N, K, _p(C), ldc, _p(C2), ldc2, _p(R), ldr, _p(bias),
+          _p(gate), ldgate, rows_per_gate, _stream())
+
+
 def wgrad_group(problems, tokens, accumulate=False):
     """problems: [(dy [tokens, n_out], x [tokens, k_in], dw f32 [n_out, k_in], dbias f32 [n_out] | None, n_out, k_in), ...]
     (tensors or raw device addresses) -> one launch of the 256x128 / 128x256 TN tiles, no split-K (reed_wgrad_group).

@@ -4,8 +4,9 @@ classifier-free guidance over the whole interval (every model evaluation at batc
 Times a short run (default 8 Heun steps = 15 evaluations) and scales to the 250-step recipe (499 evaluations): the
 per-evaluation cost does not depend on the step index. Reports generated images/s, model evaluations/s and the
 fraction of the bf16 MFMA roofline (237.23 GFLOP per image per evaluation).
-usage (GPU box): python tools/bench_generate.py [n_per_gpu] [steps] [fp16|bf16]   (fp16 = generate.py's default: the
-IEEE-half build of the kernels, the mantissa of the reference's TF32 evaluations)"""
+usage (GPU box): python tools/bench_generate.py [n_per_gpu] [steps] [fp16|bf16|fp8]   (fp16 = generate.py's default: the
+IEEE-half build of the kernels, the mantissa of the reference's TF32 evaluations; fp8 = generate.py --sample-precision fp8: that
+build with the blocks' linears as MX-fp8 block GEMMs)"""
 import json
 import os
 import sys
@@ -25,7 +26,7 @@ dev = torch.device("cuda")
 torch.manual_seed(0)
 model = SiT_models["SiT-XL/2"](z_dims=[1024], z_types=["i"], encoder_depth=8, use_cfg=True).to(dev).eval()
 random_fill(model, 1234)
-model.precision = precision
+model.precision, model.fp8 = ("fp16", True) if precision == "fp8" else (precision, False)
 z = torch.randn(n, 4, 32, 32, device=dev)
 y = torch.randint(0, 1000, (n,), device=dev)
 euler_sampler(model, z, y, num_steps=2, heun=True, cfg_scale=1.5)   # warm-up
