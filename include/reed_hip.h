@@ -314,6 +314,24 @@ int reed_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, voi
                    int64_t n_train, int64_t n_total, const float* norm_clip, const float* scaler_state, float lr,
                    float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2, float ema_decay,
                    void* stream);
+/* The two passes above over a SET of ranges of the arena (a partly frozen model: only the trainable parameters enter the norm and
+ * are updated).  ranges: a DEVICE array of nranges int64 pairs [begin, end) in arena elements, sorted, disjoint, every bound a
+ * multiple of 4 (arena segments are 8-aligned, so merged parameter ranges are), at most 1024 pairs; ranges_host: the same table in
+ * HOST memory, which is what the argument checks read (unsorted, overlapping, empty, misaligned, past the end, too many: REED_ERR_ARG,
+ * nothing launched) — the device copy is read by the kernel alone, so the call stays asynchronous.
+ * reed_grad_sqnorm_ranges: partial[nblocks] = squared-norm partials over the union of the ranges inside g[0, n), for
+ * reed_clip_finalize{,_scaled}; a fixed assignment of elements to blocks (the union numbered in arena order and dealt as
+ * reed_grad_sqnorm deals [0, n)), no atomics, every block writes its partial (0 when idle).
+ * reed_adamw_ema_ranges: reed_adamw_ema where elements of [0, n_train) inside a range get exactly its AdamW arithmetic and every
+ * other element keeps p, m and v bit for bit (no weight decay, no moment decay); the EMA lerp and the 16-bit shadow still cover
+ * [0, n_total); the same loss-scaler skip.  offset = the arena element p[0] (and g, m, v, ema, shadow [0]) stands for: a call on one
+ * update chunk passes offset pointers and the whole table, or the part of it that meets the chunk. */
+int reed_grad_sqnorm_ranges(const float* g, const int64_t* ranges, const int64_t* ranges_host, int nranges, int64_t n,
+                            float* partial, int nblocks, void* stream);
+int reed_adamw_ema_ranges(float* p, const float* g, float* m, float* v, float* ema, void* shadow,
+                          int64_t n_train, int64_t n_total, const float* norm_clip, const float* scaler_state, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, float bc1, float bc2, float ema_decay,
+                          const int64_t* ranges, const int64_t* ranges_host, int nranges, int64_t offset, void* stream);
 int reed_cast_bf16(const float* src, void* dst, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

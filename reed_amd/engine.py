@@ -18,6 +18,7 @@ import types
 import torch
 
 from . import ops
+from .freeze import FreezePlan
 from .ops import (NT, NN, TN, EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB,
                   EPI_GELU_G, EPI_SILU_G, EPI_MUL)
 
@@ -65,8 +66,8 @@ class Engine:
         self.reducer = None      # set by reed_amd.parallel.GradReducer
         self._dot_delta = {}     # (tokens, operand type, reducing, forced tile, CU reserve, comm forms) -> the dO GEMM has the head-dot epilogue
         self._ws = None
-        self._named = None       # [(name, parameter)] and the first trainable parameter, cached for backward
-        self._sentinel = None
+        self._named = None       # [(name, parameter)], cached: named_parameters() walks the module tree
+        self._plans = {}         # (requires_grad signature, x needs grad, t needs grad) -> FreezePlan
         self._ws_side = None
         self._shadow_t = None
         self.dgrad_nt = None     # True / False / None = by DGRAD_NT_MIN_TOKENS: the blocks' dgrads as NT GEMMs on transposed weights
@@ -156,15 +157,17 @@ class Engine:
                   "mlp.fc2": (EPI_GATE_RES, D, Hm)}
         return {n: ops.gemm_mxfp8_plan(e, M, N, K, precision=prec) for n, (e, N, K) in shapes.items()}
 
-    def forward(self, x, t, y, inference, need_grad, drop):
+    def forward(self, x, t, y, inference, need_grad, drop, plan=None):
+        """plan: the FreezePlan of this forward's backward (need_grad only; None = every block saves, as with every parameter
+        trainable)."""
         prec = getattr(self.m, "precision", "bf16")
         if need_grad and getattr(self.m, "fp8", False):
             raise RuntimeError("reed_amd.SiT: fp8 is a sampling mode (inference forward under torch.no_grad()); a forward that "
                                "builds a graph (training, input gradients) needs model.fp8 = False")
         with ops.build(prec, bool(getattr(self.m, "tf32", False))):
-            return self._forward(x, t, y, inference, need_grad, drop, prec)
+            return self._forward(x, t, y, inference, need_grad, drop, prec, plan)
 
-    def _forward(self, x, t, y, inference, need_grad, drop, prec):
+    def _forward(self, x, t, y, inference, need_grad, drop, prec, plan=None):
         m, L = self.m, self.L
         ops.require_cuda(x, "x")
         dev = x.device
@@ -194,7 +197,9 @@ class Engine:
 
         sag = self.save_act_grad if self.save_act_grad is not None else M > self.SAVE_ACT_GRAD_MIN_TOKENS
         self._sag = sag   # (the projector forward of this call follows it)
-        tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, t=t, prec=prec, act_grad=sag) if need_grad else None
+        tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, t=t, prec=prec, act_grad=sag, plan=plan) if need_grad else None
+        # a partly frozen model (freeze.py): blocks below the lowest one whose backward runs save nothing
+        save = plan.save if (need_grad and plan is not None) else [need_grad] * self.depth
         # epilogues of a layer whose saved array feeds the backward (gemm.h): derivative-saving forms when there is a backward
         epi_silu = EPI_SILU_G if need_grad and sag else EPI_SILU
         epi_gelu = EPI_GELU_G if need_grad and sag else EPI_GELU
@@ -236,7 +241,7 @@ class Engine:
             tp.sin, tp.t1p, tp.t1, tp.labels_eff, tp.c, tp.silu_c, tp.mod = sin, t1p, t1, labels_eff, c, silu_c, mod
 
         # -- blocks
-        if not need_grad:  # inference: ping-pong buffers, nothing saved
+        if not all(save):  # inference, blocks without a backward: ping-pong buffers, nothing saved
             xa, xb = tok, f32(M, D)
             h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
         # fp8 sampling (SiT.fp8; inference branch, 16-bit builds): the block linears that reed_gemm_mxfp8 takes at this token count run
@@ -272,7 +277,7 @@ class Engine:
                 kh = 0
             if pend:
                 self.A.wait(f"block{i}")
-            if need_grad:
+            if save[i]:
                 h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
                 h2, a1, y1, y2 = bf(M, D), bf(M, Hm), bf(M, D), bf(M, D)
                 mean1, rstd1, mean2, rstd2 = f32(M), f32(M), f32(M), f32(M)
@@ -292,7 +297,7 @@ class Engine:
             qkv_a, qstats = qkv, None
             if m.qk_norm:
                 qkv_a = bf(M, 3 * D)
-                qstats = f32(M, 2, H, 2) if need_grad else None
+                qstats = f32(M, 2, H, 2) if save[i] else None
                 ops.qk_norm_fwd(qkv, self.Wf(b + "attn.q_norm.weight"), self.Wf(b + "attn.q_norm.bias"),
                                 self.Wf(b + "attn.k_norm.weight"), self.Wf(b + "attn.k_norm.bias"), qkv_a, qstats, M, H, hd)
             ops.attention_fwd(qkv_a, o, lse, B, T, H, hd)
@@ -305,14 +310,16 @@ class Engine:
             if "mlp.fc1" in mx_on:
                 mx_gemm(b + "mlp.fc1", EPI_GELU, h2, Hm, D, None, 0, C2=u, ldc2=Hm)
             else:
-                ops.gemm(NT, epi_gelu, h2, self.W(b + "mlp.fc1.weight"), M, Hm, D, a1, D, D, Hm, C2=u, ldc2=Hm,
+                ops.gemm(NT, epi_gelu if save[i] else EPI_GELU, h2, self.W(b + "mlp.fc1.weight"), M, Hm, D, a1, D, D, Hm, C2=u, ldc2=Hm,
                          bias=self.W(b + "mlp.fc1.bias"))
             if "mlp.fc2" in mx_on:
                 mx_gemm(b + "mlp.fc2", EPI_GATE_RES, u, D, Hm, xout, D, R=xmid, ldr=D, gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
             else:
                 ops.gemm(NT, EPI_GATE_RES, u, self.W(b + "mlp.fc2.weight"), M, D, Hm, xout, Hm, Hm, D, C2=y2, ldc2=D,
                          R=xmid, ldr=D, bias=self.W(b + "mlp.fc2.bias"), gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
-            if need_grad:
+            if need_grad and not save[i]:
+                tp.blocks.append(None)
+            elif need_grad:
                 tp.blocks.append(types.SimpleNamespace(x=xcur, mean1=mean1, rstd1=rstd1, h=h, qkv=qkv, qkv_a=qkv_a,
                                                        qstats=qstats, o=o, lse=lse,
                                                        y1=y1, xmid=xmid, mean2=mean2, rstd2=rstd2, h2=h2, a1=a1, u=u,
@@ -321,7 +328,7 @@ class Engine:
             if not inference:
                 for j, dj in enumerate(self.tap_depth):
                     if dj == i + 1:
-                        zs_by_proj[j] = self._projector_fwd(j, xcur, B, need_grad, tp)
+                        zs_by_proj[j] = self._projector_fwd(j, xcur, B, need_grad and (plan is None or plan.proj[j]["run"]), tp)
         # -- final layer
         if kh:   # depth <= ADA_HEAD_BLOCKS: the tail (final layer's rows) was never launched
             self.A.wait("ada_tail")
@@ -444,6 +451,9 @@ class Engine:
         prec = getattr(self.m, "precision", "bf16")
         if getattr(tp, "prec", prec) != prec:
             raise RuntimeError("reed_amd.SiT: model.precision changed between forward and backward")
+        if tp.plan is not None and tp.plan.sig != self.signature():
+            raise RuntimeError("reed_amd.SiT: a parameter's requires_grad changed between forward and backward; the forward saved "
+                               "what the plan of that moment needs (reed_amd/freeze.py). Run the forward again")
         if frozen and self.reducer is not None:
             raise RuntimeError(FROZEN_WITH_REDUCER)
         prev = ops.use(prec)
@@ -465,8 +475,10 @@ class Engine:
 
     def _backward(self, tp, dout, dzs, hdt, need_x, need_t, wgrads):
         """wgrads = False (the frozen-weight backward): every launch that only feeds a parameter gradient is skipped; what is
-        left runs as it does with them."""
+        left runs as it does with them.  In between, the tape's FreezePlan (freeze.py) decides launch by launch, and where the
+        activation-gradient chain stops."""
         m, L = self.m, self.L
+        pl = tp.plan if tp.plan is not None else self.plan_for(need_x, need_t)
         D, H, hd, Hm, T, P, C = self.D, self.H, self.hd, self.Hm, self.T, self.P, self.C
         B = tp.B
         M = B * T
@@ -488,7 +500,7 @@ class Engine:
         def f32(*s):
             return torch.empty(s, dtype=torch.float32, device=dev)
 
-        group_wgrad = wgrads and ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
+        group_wgrad = wgrads and any(pl.group) and ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
         nws = ops.attention_bwd_ws_floats(B, T, H)       # delta = rowsum(dO * O) of the persistent attention backward
         attn_ws = f32(nws) if nws else None
         # the answer of the library ("this shape's dO GEMM has the head-dot epilogue") depends on which kernel the GEMM runs on:
@@ -507,11 +519,14 @@ class Engine:
         dout = dout.contiguous().float()
         # -- final layer
         mf = mp + hb * (self.depth * 6 * D)
-        hbuf, dlin, dh = bf(M, D), bf(M, self.NO), bf(M, D)
-        ops.final_layer_bwd_rows(dout, tp.x_last, tp.meanF, tp.rstdF, mf, mf + hb * D, Nall,
-                                 self.W("final_layer.linear.weight"), hbuf, dlin, dh, B, T, D, C, P)
-        dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-        partF = f32(M // 16, 2, D)
+        dx = None
+        if pl.final_run:
+            hbuf, dlin, dh = bf(M, D), bf(M, self.NO), bf(M, D)
+            ops.final_layer_bwd_rows(dout, tp.x_last, tp.meanF, tp.rstdF, mf, mf + hb * D, Nall,
+                                     self.W("final_layer.linear.weight"), hbuf, dlin, dh, B, T, D, C, P)
+        if pl.final_ln:
+            dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
+            partF = f32(M // 16, 2, D)
         # which projectors fire after block i's output?
         pending = {j: d for j, d in enumerate(self.tap_depth)}
 
@@ -522,7 +537,7 @@ class Engine:
             """LayerNorm+modulate backward into dx. nxt = index of the block whose MLP-branch gate consumes the finished
             dx next (or None): its gate backward rides along in the same pass unless a projector tap adds into dx in
             between. Returns (dy2, pg2) of that block when fused."""
-            if nxt is None or nxt < 0 or tap_fires(nxt + 1):
+            if nxt is None or nxt < pl.k or tap_fires(nxt + 1):
                 ops.ln_modulate_bwd(dh_, x_, mean_, rstd_, scale_ptr, Nall, dx, part_, M, D, T)
                 return None
             nb_ = tp.blocks[nxt]
@@ -531,29 +546,36 @@ class Engine:
                                      mp + hb * (nxt * 6 * D + 5 * D), Nall, dy_, pg_, None, M, D, T)
             return dy_, pg_
 
-        pre = ln_bwd(dh, tp.x_last, tp.meanF, tp.rstdF, mf + hb * D, partF, self.depth - 1)
-        if wgrads:
+        pre = ln_bwd(dh, tp.x_last, tp.meanF, tp.rstdF, mf + hb * D, partF, self.depth - 1) if pl.final_ln else None
+        if pl.final_w:
             wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, C * P * P)), dev)
             ops.smallk_wgrad(hbuf, False, dlin, wsf, self.G("final_layer.linear.weight"), None,
                              self.G("final_layer.linear.bias"), M, D, self.NO, 1, acc)
-        dmod = bf(B, Nall)
+        # the modulation gradients of every block + the final layer; truncated, only trainable adaLN rows are reduced into it and
+        # the stacked weight-gradient GEMM reads zeros elsewhere
+        dmod = None
+        if pl.dmod:
+            dmod = torch.zeros(B, Nall, dtype=hdt, device=dev) if pl.trunc else bf(B, Nall)
         offF = self.depth * 6 * D
-        ops.reduce_mod_parts([(partF.data_ptr(), 2 * D, offF), (partF.data_ptr() + 4 * D, 2 * D, offF + D)], dmod, Nall,
-                             B, D, ch)
-        del hbuf, dlin, dh
+        if pl.final_ln and pl.mod_reduce[self.depth]:
+            ops.reduce_mod_parts([(partF.data_ptr(), 2 * D, offF), (partF.data_ptr() + 4 * D, 2 * D, offF + D)], dmod, Nall,
+                                 B, D, ch)
+        if pl.final_run:
+            del hbuf, dlin, dh
         # With a reducer attached the adaLN weight gradient is computed block by block (rows of block i right after
         # block i's backward: dW_ada[i] = dmod[:, i]^T silu(c), a K = b GEMM) instead of one GEMM at the end, so each
         # slice's all-reduce overlaps the rest of backward; the arithmetic per output element is the same.
-        split_ada = wgrads and (self.reducer is not None if self.split_ada_wgrad is None else self.split_ada_wgrad)
+        split_ada = pl.any_ada and (self.reducer is not None if self.split_ada_wgrad is None else self.split_ada_wgrad)
         gp = self.A.grad.data_ptr() if wgrads else None
-        dmp = dmod.data_ptr()
+        dmp = dmod.data_ptr() if dmod is not None else None
         # Factor path (a reducer that is reducing THIS backward, no gradient accumulation in flight): the adaLN weight
         # gradient contracts over the local batch only, so instead of all-reducing the [Nall, D] fp32 matrix (a third of
         # the payload) the ranks all-gather the two bf16 factors — dmod rows of block i (pre-scaled by 1 / world: exact,
         # power-of-two worlds only) right after block i's backward, silu(c) once — and every rank forms the global-batch
         # product itself at the end of backward (K = world * b). At world = 1 this is the per-block GEMM on a copy.
         red = self.reducer
-        fg = (red is not None and red.ada_gather and red.active() and not acc and self.split_ada_wgrad is None)
+        fg = (red is not None and red.ada_gather and red.active() and not acc and self.split_ada_wgrad is None and wgrads
+              and not pl.trunc)   # (truncated: the all-reduced per-block slices; the same plan on every rank)
         if fg:
             split_ada = False
             W = red.world
@@ -579,7 +601,7 @@ class Engine:
         def ada_after(i):
             if fg:
                 ada_gather(i)
-            elif split_ada:
+            elif split_ada and pl.ada[i]:
                 ada_wgrad(i)
 
         ada_after(self.depth)
@@ -588,20 +610,23 @@ class Engine:
             if split_ada:
                 self.reducer.ready(f"ada{self.depth}")
         proj_left = len([j for j in pending if j in tp.proj])
+        proj_fired = False
         dz_by_proj = {}
         if dzs is not None:
             for k, j in enumerate(tp.zs_order):
                 dz_by_proj[j] = dzs[k]
-        for i in reversed(range(self.depth)):
+        for i in reversed(range(pl.k, self.depth)):
             for j, dj in pending.items():
                 if dj == i + 1 and j in tp.proj:
-                    self._projector_bwd(j, tp, dz_by_proj.get(j), dx, B, acc, dev, wgrads)
+                    self._projector_bwd(j, tp, dz_by_proj.get(j), dx, B, acc, dev, pl.proj[j])
                     proj_left -= 1
                     if proj_left == 0 and self.reducer is not None:
                         self.reducer.ready("projectors")
+                        proj_fired = True
             bk = tp.blocks[i]
             b = f"blocks.{i}."
             mb = mp + hb * (i * 6 * D)
+            last, lin = pl.stage[i], pl.lin[i]   # the stage this block's backward stops behind; which linears want their gradients
             # MLP branch (its gate backward usually came with the previous LayerNorm backward)
             # (bias gradients of fc2 / proj = column sums of dy2 / dy1: fused into their weight-gradient GEMMs)
             if pre is not None:
@@ -609,68 +634,75 @@ class Engine:
             else:
                 pg2, dy2 = f32(M // 16, D), bf(M, D)
                 ops.gate_bwd(dx, bk.y2, mb + 5 * hb * D, Nall, dy2, pg2, M, D, T)
-            wg = [] if group_wgrad else None   # the block's four weight gradients: one launch at the end of the block
+            pre = None
+            # the block's four weight gradients: one launch at the end of the block where all four are wanted
+            wg = [] if group_wgrad and pl.group[i] else None
             if wg is not None:
                 wg.append((dy2, bk.u, b + "mlp.fc2.weight", D, Hm))
-            elif wgrads:
+            elif lin["mlp.fc2"]:
                 self._wgrad(dy2, bk.u, b + "mlp.fc2.weight", M, D, Hm, acc, dev, side=side)
-            da1 = bf(M, Hm)
-            self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
-            if wg is not None:
-                wg.append((da1, bk.h2, b + "mlp.fc1.weight", Hm, D))
-            elif wgrads:
-                self._wgrad(da1, bk.h2, b + "mlp.fc1.weight", M, Hm, D, acc, dev, side=side)
-            # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
-            dh2 = dy2 if side is None and wg is None else bf(M, D)
-            self._dgrad(EPI_BF16, da1, b + "mlp.fc1.weight", M, Hm, D, dh2)
-            # LN2 backward + the attention branch's gate backward in one pass over dx
-            pl2 = f32(M // 16, 2, D)
-            pg1, dy1 = f32(M // 16, D), bf(M, D)
-            ops.ln_modulate_bwd_gate(dh2, bk.xmid, bk.mean2, bk.rstd2, mb + 4 * hb * D, Nall, dx, pl2, bk.y1, mb + 2 * hb * D, Nall,
-                                     dy1, pg1, None, M, D, T)
-            if wg is not None:
-                wg.append((dy1, bk.o, b + "attn.proj.weight", D, D))
-            elif wgrads:
-                self._wgrad(dy1, bk.o, b + "attn.proj.weight", M, D, D, acc, dev, side=side)
-            do = bf(M, D)
-            dqkv = bf(M, 3 * D)
-            # delta = rowsum(dO * O) of the attention backward where dO is produced: the GEMM's epilogue 13 leaves per-row,
-            # per-head partial dot products with O (12 MB instead of a 302 MB row pass over dO and O at b = 256); where this
-            # shape's GEMM kernel has no such epilogue (False, decided once per token count) the plain store + the row kernel
-            fused = False
-            if dot_delta.get(dkey, True) and attn_ws is not None:
-                dpart = f32(M * H * (1 if hd == 64 else 2))
-                fused = dot_delta[dkey] = ops.dgrad_with_head_dots(dy1, self.W(b + "attn.proj.weight"), do, bk.o, dpart, M, D, D, hd,
-                                                                   wt=self.WT(b + "attn.proj.weight"))
-            if fused:
-                ops.attention_bwd_dp(bk.qkv_a, do, bk.lse, dpart, dqkv, attn_ws, B, T, H, hd)
-            else:
-                self._dgrad(EPI_BF16, dy1, b + "attn.proj.weight", M, D, D, do)
-                ops.attention_bwd(bk.qkv_a, bk.o, do, bk.lse, dqkv, B, T, H, hd, ws=attn_ws)
-            if m.qk_norm:  # back through the per-head LayerNorm of q and k; parameter grads via per-block partials
-                nb = (M * 3 * H + 255) // 256
-                part = f32(nb, 4 * hd)
-                dpre = bf(M, 3 * D)
-                ops.qk_norm_bwd(dqkv, bk.qkv, bk.qstats, self.Wf(b + "attn.q_norm.weight"),
-                                self.Wf(b + "attn.k_norm.weight"), dpre, part, M, H, hd)
-                if wgrads:
-                    ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, acc,
-                                   ws=self.ws((nb + 63) // 64 * 4 * hd, dev))
-                dqkv = dpre
-            if wg is not None:
-                wg.append((dqkv, bk.h, b + "attn.qkv.weight", 3 * D, D))
-                self._wgrad_block(wg, M, acc, dev, side)
-            elif wgrads:
-                self._wgrad(dqkv, bk.h, b + "attn.qkv.weight", M, 3 * D, D, acc, dev, side=side)
-            dh1 = do  # reuse
-            self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)
-            pl1 = f32(M // 16, 2, D)
-            pre = ln_bwd(dh1, bk.x, bk.mean1, bk.rstd1, mb + hb * D, pl1, i - 1)
-            o6 = i * 6 * D
-            p1, p2 = pl1.data_ptr(), pl2.data_ptr()
-            ops.reduce_mod_parts([(p1, 2 * D, o6), (p1 + 4 * D, 2 * D, o6 + D), (pg1.data_ptr(), D, o6 + 2 * D),
-                                  (p2, 2 * D, o6 + 3 * D), (p2 + 4 * D, 2 * D, o6 + 4 * D),
-                                  (pg2.data_ptr(), D, o6 + 5 * D)], dmod, Nall, B, D, ch)
+            if last >= 2:
+                da1 = bf(M, Hm)
+                self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
+                if wg is not None:
+                    wg.append((da1, bk.h2, b + "mlp.fc1.weight", Hm, D))
+                elif lin["mlp.fc1"]:
+                    self._wgrad(da1, bk.h2, b + "mlp.fc1.weight", M, Hm, D, acc, dev, side=side)
+            if last >= 3:
+                # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
+                dh2 = dy2 if side is None and wg is None else bf(M, D)
+                self._dgrad(EPI_BF16, da1, b + "mlp.fc1.weight", M, Hm, D, dh2)
+                # LN2 backward + the attention branch's gate backward in one pass over dx
+                pl2 = f32(M // 16, 2, D)
+                pg1, dy1 = f32(M // 16, D), bf(M, D)
+                ops.ln_modulate_bwd_gate(dh2, bk.xmid, bk.mean2, bk.rstd2, mb + 4 * hb * D, Nall, dx, pl2, bk.y1, mb + 2 * hb * D, Nall,
+                                         dy1, pg1, None, M, D, T)
+                if wg is not None:
+                    wg.append((dy1, bk.o, b + "attn.proj.weight", D, D))
+                elif lin["attn.proj"]:
+                    self._wgrad(dy1, bk.o, b + "attn.proj.weight", M, D, D, acc, dev, side=side)
+            if last >= 4:
+                do = bf(M, D)
+                dqkv = bf(M, 3 * D)
+                # delta = rowsum(dO * O) of the attention backward where dO is produced: the GEMM's epilogue 13 leaves per-row,
+                # per-head partial dot products with O (12 MB instead of a 302 MB row pass over dO and O at b = 256); where this
+                # shape's GEMM kernel has no such epilogue (False, decided once per token count) the plain store + the row kernel
+                fused = False
+                if dot_delta.get(dkey, True) and attn_ws is not None:
+                    dpart = f32(M * H * (1 if hd == 64 else 2))
+                    fused = dot_delta[dkey] = ops.dgrad_with_head_dots(dy1, self.W(b + "attn.proj.weight"), do, bk.o, dpart, M, D, D, hd,
+                                                                       wt=self.WT(b + "attn.proj.weight"))
+                if fused:
+                    ops.attention_bwd_dp(bk.qkv_a, do, bk.lse, dpart, dqkv, attn_ws, B, T, H, hd)
+                else:
+                    self._dgrad(EPI_BF16, dy1, b + "attn.proj.weight", M, D, D, do)
+                    ops.attention_bwd(bk.qkv_a, bk.o, do, bk.lse, dqkv, B, T, H, hd, ws=attn_ws)
+                if m.qk_norm:  # back through the per-head LayerNorm of q and k; parameter grads via per-block partials
+                    nb = (M * 3 * H + 255) // 256
+                    part = f32(nb, 4 * hd)
+                    dpre = bf(M, 3 * D)
+                    ops.qk_norm_bwd(dqkv, bk.qkv, bk.qstats, self.Wf(b + "attn.q_norm.weight"),
+                                    self.Wf(b + "attn.k_norm.weight"), dpre, part, M, H, hd)
+                    if pl.qknorm[i]:
+                        ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, acc,
+                                       ws=self.ws((nb + 63) // 64 * 4 * hd, dev))
+                    dqkv = dpre
+                if wg is not None:
+                    wg.append((dqkv, bk.h, b + "attn.qkv.weight", 3 * D, D))
+                    self._wgrad_block(wg, M, acc, dev, side)
+                elif lin["attn.qkv"]:
+                    self._wgrad(dqkv, bk.h, b + "attn.qkv.weight", M, 3 * D, D, acc, dev, side=side)
+            if last >= 5:
+                dh1 = do  # reuse
+                self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)
+                pl1 = f32(M // 16, 2, D)
+                pre = ln_bwd(dh1, bk.x, bk.mean1, bk.rstd1, mb + hb * D, pl1, i - 1)
+                if pl.mod_reduce[i]:
+                    o6 = i * 6 * D
+                    p1, p2 = pl1.data_ptr(), pl2.data_ptr()
+                    ops.reduce_mod_parts([(p1, 2 * D, o6), (p1 + 4 * D, 2 * D, o6 + D), (pg1.data_ptr(), D, o6 + 2 * D),
+                                          (p2, 2 * D, o6 + 3 * D), (p2 + 4 * D, 2 * D, o6 + 4 * D),
+                                          (pg2.data_ptr(), D, o6 + 5 * D)], dmod, Nall, B, D, ch)
             tp.blocks[i] = None  # free this block's activations
             ada_after(i)
             if self.reducer is not None:
@@ -684,6 +716,8 @@ class Engine:
                         self.reducer.ready(f"block{i}")
                         if split_ada:
                             self.reducer.ready(f"ada{i}")
+        if pl.trunc:
+            return self._backward_truncated_end(tp, pl, pending, dz_by_proj, proj_fired, B, acc, dev, side, split_ada, dmod, gp)
         if proj_left > 0 and m.z_dims and self.reducer is not None:   # projector outputs unused by the loss
             self.reducer.ready("projectors")
         # -- adaLN (all blocks + final): dW = dmod^T silu(c); d silu(c) = dmod @ W   (one GEMM each)
@@ -694,7 +728,7 @@ class Engine:
                 c0, rows = ada_rows(i)
                 ops.gemm(TN, EPI_F32, g_recv.data_ptr() + hb * W * B * c0, s_all, rows, D, W * B,
                          gp + 4 * (L.ada_w_off + c0 * D), rows, D, D, dbias=gp + 4 * (L.ada_b_off + c0), accumulate=False)
-        elif wgrads and not split_ada:
+        elif pl.any_ada and not split_ada:
             ops.gemm(TN, EPI_F32, dmod, tp.silu_c, Nall, D, B, gp + 4 * L.ada_w_off, Nall, D, D,
                      dbias=gp + 4 * L.ada_b_off, accumulate=acc)
         ksteps = Nall // 64
@@ -709,19 +743,20 @@ class Engine:
         # -- conditioning: label table + timestep MLP
         dtemb = bf(B, D)
         gt = None   # a frozen table: no scatter
-        if wgrads:
+        if pl.label:
             gt = self.A.view(self.A.grad, "y_embedder.embedding_table.weight")
             if not acc:
                 gt.zero_()
         ops.label_cond_bwd(dsilu, tp.c, tp.labels_eff, dtemb, gt, B, D)
-        if wgrads:
+        if pl.t2:
             ops.linear_wgrad(dtemb, tp.t1, self.G("t_embedder.mlp.2.weight"), dbias=self.G("t_embedder.mlp.2.bias"),
                              accumulate=acc, Mtok=B, N=D, K=D)
         dt1 = bf(B, D)
         ops.gemm(NN, EPI_MUL if tp.act_grad else EPI_DSILU, dtemb, self.W("t_embedder.mlp.2.weight"), B, D, D, dt1, D, D, D, R=tp.t1p, ldr=D)
-        if wgrads:
+        if pl.t0:
             ops.linear_wgrad(dt1, tp.sin, self.G("t_embedder.mlp.0.weight"), dbias=self.G("t_embedder.mlp.0.bias"),
                              accumulate=acc, Mtok=B, N=D, K=256)
+        if pl.x_emb:
             # -- patch embed: dW[d,k] = sum_tokens bf16(dx)[token,d] * patch[token,k]
             K = C * P * P
             xb = bf(M, K)
@@ -756,14 +791,47 @@ class Engine:
             self._attach_grads()
         return dx_in, dt_in
 
-    def _projector_bwd(self, j, tp, dz, dx, B, acc, dev, wgrads=True):
+    def _backward_truncated_end(self, tp, pl, pending, dz_by_proj, proj_fired, B, acc, dev, side, split_ada, dmod, gp):
+        """The end of a truncated backward (FreezePlan.trunc): the projector chains whose tap lies at or below the lowest block that
+        ran (weight gradients only: nothing consumes their dx), the stacked adaLN weight gradient where no reducer takes it in
+        slices, and every gradient bucket that has not fired yet, in the fixed order of the full backward."""
+        L, D = self.L, self.D
+        for j, dj in sorted(pending.items(), key=lambda it: -it[1]):
+            if dj <= pl.k and j in tp.proj and tp.proj[j] is not None:
+                self._projector_bwd(j, tp, dz_by_proj.get(j), None, B, acc, dev, pl.proj[j])
+        if pl.any_ada and not split_ada:
+            Nall = L.ada_rows
+            ops.gemm(TN, EPI_F32, dmod, tp.silu_c, Nall, D, B, gp + 4 * L.ada_w_off, Nall, D, D,
+                     dbias=gp + 4 * L.ada_b_off, accumulate=acc)
+        if side is not None:
+            torch.cuda.current_stream().wait_stream(side)
+        if self.reducer is not None:
+            for i in reversed(range(pl.k)):
+                self.reducer.ready(f"block{i}")
+                if split_ada:
+                    self.reducer.ready(f"ada{i}")
+            if self.m.z_dims and not proj_fired and hasattr(tp, "zs_order"):
+                self.reducer.ready("projectors")
+            if not split_ada:
+                for i in reversed(range(self.depth + 1)):
+                    self.reducer.ready(f"ada{i}")
+            self.reducer.ready("embed")
+        self.grad_live = True
+        self._attach_grads()
+        return None, None
+
+    def _projector_bwd(self, j, tp, dz, dx, B, acc, dev, pj=None):
+        """pj: the plan's entry for this projector (freeze.py) — which layers want their weight gradient, the layer the chain
+        stops behind, whether the tap's contribution to the trunk's dx is formed; None = everything."""
         m, D, T = self.m, self.D, self.T
         Pd, Z = m.projector_dim, m.z_dims[j]
-        pj = tp.proj[j]
-        R = pj.R
+        pr = tp.proj[j]
+        R = pr.R
         pre = f"projectors.{j}."
+        w = pj["w"] if pj is not None else {4: True, 2: True, 0: True}
+        stop = pj["stop"] if pj is not None else -1
         if dz is None:  # projector output unused by the loss: zero grads (torch would leave them None)
-            if wgrads and not acc:
+            if any(w.values()) and not acc:
                 b, e = self.L.range_of(pre)
                 self.A.grad[b:e].zero_()
             return
@@ -773,33 +841,59 @@ class Engine:
             dz = dz.to(hdt)
         dz = dz.contiguous()
         bf = lambda *s: torch.empty(s, dtype=hdt, device=dev)  # noqa: E731
-        if wgrads:
-            self._wgrad(dz, pj.p2, pre + "4.weight", R, Z, Pd, acc, dev)
+        tp.proj[j] = None
+        if w[4]:
+            self._wgrad(dz, pr.p2, pre + "4.weight", R, Z, Pd, acc, dev)
+        if stop == 4:
+            return
         d2 = bf(R, Pd)
         epi_dsilu = EPI_MUL if tp.act_grad else EPI_DSILU
-        ops.gemm(NN, epi_dsilu, dz, self.W(pre + "4.weight"), R, Pd, Z, d2, Z, Pd, Pd, R=pj.p2p, ldr=Pd)
-        if wgrads:
-            self._wgrad(d2, pj.p1, pre + "2.weight", R, Pd, Pd, acc, dev)
+        ops.gemm(NN, epi_dsilu, dz, self.W(pre + "4.weight"), R, Pd, Z, d2, Z, Pd, Pd, R=pr.p2p, ldr=Pd)
+        if w[2]:
+            self._wgrad(d2, pr.p1, pre + "2.weight", R, Pd, Pd, acc, dev)
+        if stop == 2:
+            return
         d1 = bf(R, Pd)
-        ops.gemm(NN, epi_dsilu, d2, self.W(pre + "2.weight"), R, Pd, Pd, d1, Pd, Pd, Pd, R=pj.p1p, ldr=Pd)
-        if wgrads:
-            self._wgrad(d1, pj.xin, pre + "0.weight", R, Pd, D, acc, dev)
+        ops.gemm(NN, epi_dsilu, d2, self.W(pre + "2.weight"), R, Pd, Pd, d1, Pd, Pd, Pd, R=pr.p1p, ldr=Pd)
+        if w[0]:
+            self._wgrad(d1, pr.xin, pre + "0.weight", R, Pd, D, acc, dev)
+        if stop == 0:
+            return
         if m.z_types[j] == "i":
             ops.gemm(NN, EPI_ADDF32_RB, d1, self.W(pre + "0.weight"), R, D, Pd, dx, Pd, D, D)
         else:
             dmean = bf(R, D)
             ops.gemm(NN, EPI_BF16, d1, self.W(pre + "0.weight"), R, D, Pd, dmean, Pd, D, D)
             ops.token_mean_bwd(dmean, dx, B, T, D)
-        tp.proj[j] = None
 
     def _params(self):
         if self._named is None:   # named_parameters() walks the module tree (1 ms per call on SiT-XL/2): once
             self._named = [(name, p) for name, p in self.m.named_parameters()]
         return self._named
 
+    def signature(self):
+        """requires_grad of every named parameter, read afresh from the cached parameter list (no walk over the module tree)."""
+        return tuple(p.requires_grad for _, p in self._params())
+
     def any_trainable(self):
-        """Whether any parameter requires grad (pos_embed never does): read afresh from the cached parameter list."""
-        return any(p.requires_grad for _, p in self._params())
+        """Whether any parameter requires grad (pos_embed never does)."""
+        return any(self.signature())
+
+    def plan_for(self, need_x=False, need_t=False, sig=None):
+        """The FreezePlan (freeze.py) of the parameters' current requires_grad flags, cached per signature."""
+        sig = self.signature() if sig is None else sig
+        key = (sig, bool(need_x), bool(need_t))
+        plan = self._plans.get(key)
+        if plan is None:
+            names = [n for n, _ in self._params()]
+            plan = FreezePlan(self.depth, self.tap_depth, [n for n, on in zip(names, sig) if on], qk_norm=bool(self.m.qk_norm),
+                              need_x=need_x, need_t=need_t, all_names=names)
+            plan.sig = sig
+            plan.first = next((k for k, on in enumerate(sig) if on), None)   # a trainable parameter: its .grad tells whether
+            if len(self._plans) > 64:                                          # the caller dropped the gradients
+                self._plans.clear()
+            self._plans[key] = plan
+        return plan
 
     def _attach_grads(self):
         """Expose the grad arena through param.grad (views), for torch.optim / clip_grad_norm_ compatibility."""
@@ -823,9 +917,9 @@ class _SiTFunction(torch.autograd.Function):
     never sees as inputs) do; None in the frozen-weight mode, where x or t carries the graph."""
 
     @staticmethod
-    def forward(ctx, anchor, model, x, t, y, inference, drop):
+    def forward(ctx, anchor, model, x, t, y, inference, drop, plan):
         eng = model.engine()
-        out, zs, tape = eng.forward(x, t, y, inference, True, drop)
+        out, zs, tape = eng.forward(x, t, y, inference, True, drop, plan)
         ctx.eng, ctx.tape, ctx.frozen = eng, tape, anchor is None
         ctx.nz = 0 if zs is None else len(zs)
         ctx.set_materialize_grads(False)
@@ -841,17 +935,15 @@ class _SiTFunction(torch.autograd.Function):
             dout = torch.zeros_like(tape.x)
         if not ctx.frozen:
             # the user may have dropped p.grad (zero_grad(set_to_none=True)) -> overwrite semantics
-            if eng._sentinel is None:
-                eng._sentinel = next(p for p in eng.m.parameters() if p.requires_grad)
-            if eng._sentinel.grad is None:
+            if eng._params()[tape.plan.first][1].grad is None:
                 eng.grad_live = False
         need_x, need_t = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         dx, dt = eng.backward(tape, dout, list(dzs) if ctx.nz else None, need_x, need_t, ctx.frozen)
-        return None, None, dx, dt, None, None, None
+        return None, None, dx, dt, None, None, None, None
 
 
 def sit_apply(model, x, t, y, inference=True):
-    """Builds an autograd graph when gradients are enabled and the parameters are trainable, x.requires_grad or t.requires_grad;
+    """Builds an autograd graph when gradients are enabled and any parameter is trainable, x.requires_grad or t.requires_grad;
     x.grad / t.grad come back in the caller's dtype and shape (the casts below are torch's, in front of the Function).  With an
     input that requires grad and NO trainable parameter the backward is the frozen-weight one (Engine.backward)."""
     ops.require_cuda(x, "x")
@@ -862,11 +954,14 @@ def sit_apply(model, x, t, y, inference=True):
             drop = model.force_drop_mask
         elif model.training:  # LabelEmbedder.token_drop (sit.py:84-93): device RNG draw
             drop = torch.rand(y.shape[0], device=y.device) < model.class_dropout_prob
-    need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in (model.x_embedder.proj.weight,))
-    frozen = False
-    if torch.is_grad_enabled() and (x.requires_grad or t.requires_grad):
-        # the walk over every parameter only here: a partly frozen model computes all gradients, as it does without x.grad
-        need_grad, frozen = True, not eng.any_trainable()
+    need_grad, frozen, plan = False, False, None
+    if torch.is_grad_enabled():
+        sig = eng.signature()
+        frozen = not any(sig)
+        need_grad = (not frozen) or x.requires_grad or t.requires_grad
+    if need_grad:
+        plan = eng.plan_for(x.requires_grad, t.requires_grad, sig)
+    if need_grad and (x.requires_grad or t.requires_grad):
         if frozen and eng.reducer is not None:
             raise RuntimeError(FROZEN_WITH_REDUCER)
         if x.requires_grad and x.dtype != torch.float32:
@@ -880,7 +975,7 @@ def sit_apply(model, x, t, y, inference=True):
         return out, zs
     if not frozen and (not hasattr(model, "_anchor") or model._anchor.device != x.device):
         model._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-    res = _SiTFunction.apply(None if frozen else model._anchor, model, x, t, y, inference, drop)
+    res = _SiTFunction.apply(None if frozen else model._anchor, model, x, t, y, inference, drop, plan)
     out, zs = res[0], (list(res[1:]) if len(res) > 1 else None)
     if inference:
         zs = None

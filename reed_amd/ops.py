@@ -735,6 +735,36 @@ def adamw_ema(p, g, m, v, ema, shadow, n_train, n_total, norm_clip, lr, beta1, b
           _p(scaler_state), lr, beta1, beta2, eps, wd, bc1, bc2, ema_decay, _stream())
 
 
+MAX_RANGES = 1024   # csrc/optim.hip: kMaxRanges
+
+
+class Ranges:
+    """A table of [begin, end) arena ranges for the ranged optimiser passes: the device array the kernels read and the host copy
+    the entry points check (include/reed_hip.h).  pairs: any sequence of (begin, end); nothing is checked here."""
+
+    def __init__(self, pairs, device):
+        self.pairs = [(int(b), int(e)) for b, e in pairs]
+        self.host = torch.tensor(self.pairs, dtype=torch.int64).reshape(-1, 2).contiguous()
+        self.dev = self.host.to(device)
+
+    def __len__(self):
+        return len(self.pairs)
+
+
+def grad_sqnorm_ranges(g, ranges, n, partial, nblocks):
+    _call("reed_grad_sqnorm_ranges", _p(g), ranges.dev.data_ptr(), ranges.host.data_ptr(), len(ranges), n, _p(partial), nblocks,
+          _stream())
+
+
+def adamw_ema_ranges(p, g, m, v, ema, shadow, n_train, n_total, norm_clip, lr, beta1, beta2, eps, wd, bc1, bc2, ema_decay,
+                     ranges, offset=0, scaler_state=None, first=0, count=None):
+    """first / count: hand the kernel only that part of the table (the ranges that meet this call's [offset, offset + n_total))."""
+    count = len(ranges) - first if count is None else count
+    _call("reed_adamw_ema_ranges", _p(p), _p(g), _p(m), _p(v), _p(ema), _p(shadow), n_train, n_total, _p(norm_clip),
+          _p(scaler_state), lr, beta1, beta2, eps, wd, bc1, bc2, ema_decay, ranges.dev.data_ptr() + 16 * first,
+          ranges.host.data_ptr() + 16 * first, count, offset, _stream())
+
+
 # ---------------- samplers ----------------
 def sampler_input(x, out, n, dup):
     _call("reed_sampler_input", _p(x), _p(out), n, int(dup), _stream())

@@ -7,6 +7,7 @@ import os
 import torch
 
 from . import ops
+from .freeze import trainable_ranges
 
 _NB = 2048  # partial-sum blocks of the squared-norm reduction
 
@@ -35,6 +36,12 @@ class FusedAdamWEMA:
         self.lr, self.betas, self.weight_decay, self.eps = lr, tuple(betas), weight_decay, eps
         self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
         self.step_count = 0
+        # a partly frozen model (requires_grad False on some parameters): the norm and the AdamW update walk the trainable
+        # parameters' ranges only (ops.grad_sqnorm_ranges / adamw_ema_ranges); the table is rebuilt when the flags change
+        self._sig = None         # the requires_grad flags the table below was built for
+        self._ranges = None      # ops.Ranges of the trainable parameters; None = every parameter trains: the plain passes
+        self._chunk_ranges = None  # overlap mode: the same ranges cut at the update chunks, {chunk name: (first, count)}
+        self._seen = None        # flags of the first step: a parameter that trains later has missed the bias corrections
         A = model._arena
         if A.master.device.type != "cuda":
             raise RuntimeError("FusedAdamWEMA: move the model to the GPU first")
@@ -80,17 +87,24 @@ class FusedAdamWEMA:
 
     def _step(self, m, A, L, prec):
         A.ensure_shadow(prec)
+        rg = self._plan_ranges(m, L)
         self.norm_clip = self._norm_clips[(self.step_count + 1) & 1]
         nc = None
         st = self.scaler_state
         clip = self.max_grad_norm is not None and self.max_grad_norm > 0
+        def sqnorm():
+            if rg is None:
+                ops.grad_sqnorm(A.grad, L.n_train, self.partial, _NB)
+            else:
+                ops.grad_sqnorm_ranges(A.grad, rg, L.n_train, self.partial, _NB)
+
         if st is not None:        # scaled gradients: the norm pass also finds overflows, the coefficient also unscales
-            ops.grad_sqnorm(A.grad, L.n_train, self.partial, _NB)
+            sqnorm()
             ops.clip_finalize_scaled(self.partial, _NB, float(self.max_grad_norm) if clip else 0.0, self.norm_clip, st,
                                      *self.scaler_cfg)
             nc = self.norm_clip
         elif clip:
-            ops.grad_sqnorm(A.grad, L.n_train, self.partial, _NB)
+            sqnorm()
             ops.clip_finalize(self.partial, _NB, float(self.max_grad_norm), self.norm_clip)
             nc = self.norm_clip
         self.step_count += 1
@@ -100,8 +114,12 @@ class FusedAdamWEMA:
         ema_buf = self.ema._arena.master if self.ema is not None else None
         keep_t = False
         if not self.overlap and not self._want_shard:
-            ops.adamw_ema(A.master, A.grad, self.exp_avg, self.exp_avg_sq, ema_buf, A.shadow, L.n_train, L.n_total, nc,
-                          self.lr, b1, b2, self.eps, self.weight_decay, bc1, bc2, self.ema_decay, scaler_state=st)
+            if rg is None:
+                ops.adamw_ema(A.master, A.grad, self.exp_avg, self.exp_avg_sq, ema_buf, A.shadow, L.n_train, L.n_total, nc,
+                              self.lr, b1, b2, self.eps, self.weight_decay, bc1, bc2, self.ema_decay, scaler_state=st)
+            else:
+                ops.adamw_ema_ranges(A.master, A.grad, self.exp_avg, self.exp_avg_sq, ema_buf, A.shadow, L.n_train, L.n_total, nc,
+                                     self.lr, b1, b2, self.eps, self.weight_decay, bc1, bc2, self.ema_decay, rg, scaler_state=st)
         else:
             A.wait_all()
             main = torch.cuda.current_stream()
@@ -121,6 +139,23 @@ class FusedAdamWEMA:
             mp, vp = self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr()
             ep = ema_buf.data_ptr() if ema_buf is not None else None
             ev = None
+
+            if rg is not None and self._chunk_ranges is None:   # the table cut at the chunk bounds: a call sees its own part
+                cut, where = [], {}
+                for name, b, e in self._chunks:
+                    part = [(max(rb, b), min(re_, e)) for rb, re_ in rg.pairs if rb < e and re_ > b]
+                    where[name] = (len(cut), len(part))
+                    cut += part
+                self._chunk_ranges = (ops.Ranges(cut, A.master.device), where)
+
+            def update_ranged(name, b, e):
+                nt = max(0, min(e, L.n_train) - b)
+                table, where = self._chunk_ranges
+                first, count = where[name]
+                ops.adamw_ema_ranges(pp + 4 * b, gp + 4 * b if nt else None, mp + 4 * b if nt else None,
+                                     vp + 4 * b if nt else None, ep + 4 * b if ep is not None else None, sp + hb * b, nt,
+                                     e - b, nc, self.lr, b1, b2, self.eps, self.weight_decay, bc1, bc2, self.ema_decay, table,
+                                     offset=b, scaler_state=st, first=first, count=count)
 
             def update(b, e):
                 nt = max(0, min(e, L.n_train) - b)
@@ -151,7 +186,10 @@ class FusedAdamWEMA:
                         A.pending[name] = ev
                 else:
                     for name, b, e in self._chunks:
-                        update(b, e)
+                        if rg is None:
+                            update(b, e)
+                        else:
+                            update_ranged(name, b, e)
                         ev = torch.cuda.Event()
                         ev.record(side)
                         A.pending[name] = ev
@@ -169,6 +207,30 @@ class FusedAdamWEMA:
             A.shadow_t_gen = A.shadow_gen
         if self.ema is not None:
             self.ema._arena.shadow_version = -1  # EMA master changed behind torch's back: re-cast on next use
+
+    def _plan_ranges(self, m, L):
+        """The ranges table of the trainable parameters, or None when every parameter trains (the plain passes, as ever)."""
+        eng = m.engine()
+        sig = eng.signature()
+        if sig != self._sig:
+            names = [n for n, _ in eng._params()]
+            on = {n for n, f in zip(names, sig) if f}
+            if self._seen is not None:
+                late = [n for n, f, f0 in zip(names, sig, self._seen) if f and not f0]
+                if late:
+                    raise RuntimeError(f"FusedAdamWEMA: {late[0]} (and {len(late) - 1} more) became trainable after the optimiser's "
+                                       "first step. The optimiser keeps one step count for all parameters, so their bias "
+                                       "corrections would be wrong: build a new FusedAdamWEMA for the new trainable set")
+            full = on >= {n for n in names if n != "pos_embed"}
+            self._ranges = None if full else ops.Ranges(trainable_ranges(L, on), m._arena.master.device)
+            self._chunk_ranges = None
+            self._sig = sig
+        if self._ranges is not None and self._want_shard:
+            raise RuntimeError("FusedAdamWEMA: REED_OPT_SHARD=1 with a partly frozen model is not implemented (the sharded pass "
+                               "updates whole chunks); unset REED_OPT_SHARD or leave every parameter trainable")
+        # (a parameter frozen along the way has missed moment updates as well: it counts as never trained from then on)
+        self._seen = sig if self._seen is None else tuple(a and b for a, b in zip(self._seen, sig))
+        return self._ranges
 
     def _shard_plan(self, L, world=None, rank=None):
         """Sharded update (REED_OPT_SHARD=1 | auto).  The fused pass moves 38 bytes per parameter whatever

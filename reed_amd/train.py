@@ -125,10 +125,23 @@ def parse_args(input_args=None):
                         help="the activation backward: 1 = one multiply by the derivative the forward saved, 0 = recomputed from the saved "
                              "pre-activation, auto = by tokens per GPU (engine.Engine.SAVE_ACT_GRAD_MIN_TOKENS).  The two differ by one bf16 "
                              "rounding of the derivative: pin it to compare runs of one global batch on different GPU counts bit for bit")
+    part = parser.add_mutually_exclusive_group()
+    part.add_argument("--freeze", type=str, nargs="+", default=None, metavar="PATTERN",
+                      help="fine-tune part of the model: parameters whose name matches a pattern (fnmatch, e.g. 'x_embedder.*' "
+                           "'blocks.[0-9].*') get requires_grad False — no gradient launch, no AdamW update, no weight decay; the "
+                           "backward stops where nothing upstream trains (reed_amd/freeze.py).  A pattern that matches nothing is an error")
+    part.add_argument("--train-only", type=str, nargs="+", default=None, metavar="PATTERN",
+                      help="the complement: only parameters whose name matches a pattern train, e.g. 'projectors.*' or "
+                           "'final_layer.*' 'blocks.2[4-7].*'")
+    parser.add_argument("--init-from", type=str, default=None, metavar="CKPT",
+                        help="start at step 0 from the weights of a checkpoint written by this script: loads ckpt['model'] and "
+                             "ckpt['ema'], no optimiser state (--resume-step continues a run instead)")
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft checkpoint (diffusers layout): turns on the reference's preview sampling at step 1 "
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
+    if args.init_from and args.resume_step > 0:
+        parser.error("--init-from starts a new run at step 0; --resume-step continues one: pass one of the two")
     args.encoder_precision = resolve_encoder_precision(args.encoder_precision, args.mixed_precision)   # args.json holds the result
     args.gemm_tf32 = resolve_tf32(args.allow_tf32, args.mixed_precision)                               # and this one
     if args.encoder_ckpts and args.resolution != 256:
@@ -141,6 +154,17 @@ def parse_args(input_args=None):
                          f"towers run at 448 pixels); {'; '.join(why)}. At --resolution {args.resolution} pass --features-dirs, "
                          f"--packed-dir with features, or --synthetic")
     return args
+
+
+def apply_freeze(model, freeze=None, train_only=None):
+    """--freeze / --train-only on a model: requires_grad of every named parameter but pos_embed by fnmatch on its name
+    (freeze.select_parameters; a pattern that matches nothing raises).  Returns the number of trainable elements."""
+    from .freeze import select_parameters
+    named = [(n, p) for n, p in model.named_parameters() if n != "pos_embed"]
+    on = select_parameters([n for n, _ in named], freeze, train_only)
+    for n, p in named:
+        p.requires_grad_(n in on)
+    return sum(p.numel() for n, p in named if n in on)
 
 
 def resolve_tf32(allow_tf32, mixed_precision):
@@ -288,12 +312,21 @@ def main(args):
     # --allow-tf32 with "no" (train.py:249-251 sets torch.backends.cuda.matmul.allow_tf32): the fp32 GEMMs as three bf16 MFMA products
     allow_tf32 = getattr(args, "allow_tf32", False)
     model.tf32 = getattr(args, "gemm_tf32", resolve_tf32(allow_tf32, args.mixed_precision))
+    # --freeze / --train-only, before the optimiser is built (it plans its passes from the trainable set)
+    if getattr(args, "freeze", None) or getattr(args, "train_only", None):
+        n_on = apply_freeze(model, args.freeze, args.train_only)
+        logger_msg = (f"{'--freeze ' + ' '.join(args.freeze) if args.freeze else '--train-only ' + ' '.join(args.train_only)}: "
+                      f"{n_on:,} trainable parameters of {sum(p.numel() for p in model.parameters()):,}")
+    else:
+        logger_msg = None
     ema = copy.deepcopy(model).to(device)
     ema.requires_grad_(False)
     loss_fn = SILoss(prediction=args.prediction, path_type=args.path_type, enc_names=enc_names,
                      weighting=args.weighting, loss_weights={n: args.repa_coeff[i] for i, n in enumerate(enc_names)},
                      time_schedule=args.time_schedule, cutoffs=args.cutoffs, latents_scale=0.18215, latents_bias=0.0)
     logger.info(f"SiT Parameters: {sum(p.numel() for p in model.parameters()):,}")
+    if logger_msg:
+        logger.info(logger_msg)
     if model.tf32:
         logger.info("--allow-tf32: fp32 GEMMs (forward, input and weight gradients) run as three bf16 MFMA products per fp32 product, "
                     "fp32 accumulation; attention, LayerNorm, loss and optimiser stay exact fp32")
@@ -355,6 +388,11 @@ def main(args):
         ema.load_state_dict(ckpt["ema"])
         optimizer.load_state_dict(ckpt["opt"])
         global_step = ckpt["steps"]
+    elif getattr(args, "init_from", None):
+        ckpt = torch.load(args.init_from, map_location="cpu", weights_only=False)
+        model.load_state_dict(ckpt["model"])
+        ema.load_state_dict(ckpt["ema"])
+        logger.info(f"--init-from {args.init_from}: model and EMA weights of step {ckpt.get('steps', '?')}, a fresh optimiser, step 0")
     reducer = None
     if world > 1:
         reducer = GradReducer(model, rank, world)
