@@ -335,6 +335,28 @@ int reed_adamw_ema_ranges(float* p, const float* g, float* m, float* v, float* e
 int reed_cast_bf16(const float* src, void* dst, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LoRA: low-rank adapters W' = W + s B A on a block linear (csrc/lora.hip; reed_amd/lora.py).  No counterpart in the
+ * reference, whose nn.Linear a user wraps; here the adapters are merged into the GEMM operand copies, the hot GEMMs untouched.
+ * R = 8, 16, 32 or 64.  "r" rounds to the build's operand type (the identity in the fp32 build).
+ * ------------------------------------------------------------------------------------------- */
+/* w' = w + scale * sum_j b[n, j] a[j, k]: fp32, j ascending (acc = fma(b, a, acc) from 0), then w' = fma(scale, acc, w); an update
+ * that is exactly zero leaves w as it is (b == 0 reproduces r(w) bit for bit).  w f32 [N, K], a f32 [R, K], b f32 [N, R];
+ * w_op [N, K] in the operand type receives r(w'), w32 f32 [N, K] receives w'; either may be NULL (not both), either may alias
+ * nothing but itself.  One pass: 4 bytes read and 2 (+ 4) written per element of w.  K % 4 == 0. */
+int reed_lora_merge(const float* w, const float* a, const float* b, float scale, void* w_op, float* w32, int N, int K, int R,
+                    void* stream);
+/* The adapters' gradients from the linear's (dy, x) pair: x [M, K], dy [M, N], a16 [R, K], b16 [N, R] in the operand type;
+ *   u = r(scale * (x a16^T)) [M, R]     v = r(scale * (dy b16)) [M, R]       (THE SCALE IS APPLIED HERE, in fp32, before r)
+ *   db f32 [N, R] (+)= dy^T u           da f32 [R, K] (+)= v^T x             (fp32 accumulation; accumulate: one add to the prior)
+ * Fixed reduction order, no atomics: two runs give the same bits.  ws: caller-owned workspace of reed_lora_grads_ws_floats
+ * floats (-1: shape outside the domain), 16-byte aligned; nothing outside the live elements of da / db is written.
+ * 16-bit builds: N % 128 == 0, K % 128 == 0; fp32 build: N % 4 == 0, K % 4 == 0; any M >= 1.  Anything else is refused
+ * without a launch. */
+int64_t reed_lora_grads_ws_floats(int M, int N, int K, int R);
+int reed_lora_grads(const void* x, const void* dy, const void* a16, const void* b16, float scale, float* da, float* db,
+                    float* ws, int M, int N, int K, int R, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Samplers (samplers.py:46-104,107-187): fp64 state updates
  * ------------------------------------------------------------------------------------------- */
 /* d = cfg ? d_u + s (d_c - d_u) : d_c  (model out f32 [2n or n]); x_next = x_cur + dt * (w0 d + w1 d_prev)

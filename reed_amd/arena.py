@@ -54,6 +54,10 @@ class ArenaLayout:
         self.ada_b_off = self.seg[ada_b[0]][0]
         self.ada_rows = sum(shapes[n][0] for n in ada_w)
         self.depth = depth
+        # LoRA (reed_amd/lora.py): [(block, weight name, lora_A name, lora_B name)] of the adapted linears and the scale alpha / R;
+        # the adapters sit right behind their linear's bias (state_dict order), inside the block's bucket and update chunk
+        self.lora = [(int(n.split(".")[1]), n[:-len("lora_A")] + "weight", n, n[:-1] + "B") for n in order if n.endswith(".lora_A")]
+        self.lora_scale = 1.0
 
     def off(self, name):
         return self.seg[name][0]
@@ -190,11 +194,28 @@ class ParamArena:
             prev = ops.use(precision)
             try:
                 ops.cast_bf16(self.master, self.shadow, self.layout.n_total)
+                self.merge_lora()
             finally:
                 ops.use(prev)
             self.shadow_version = self.master._version
             self.shadow_gen += 1
         return self.shadow
+
+    def merge_lora(self, block=None):
+        """The shadow of every adapted weight (of one block, or of all) <- r(W + s B A) from the fp32 masters, on the current stream
+        and in the build the caller selected (csrc/lora.hip: reed_lora_merge).  Whoever rewrites the shadow calls this before
+        shadow_gen moves on, so the transposed and MX-fp8 copies follow by their own mechanism.  Reads masters only: idempotent."""
+        L = self.layout
+        if not L.lora:
+            return
+        from . import ops
+        mp, sp, es = self.master.data_ptr(), self.shadow.data_ptr(), self.shadow.element_size()
+        for i, w, a, b in L.lora:
+            if block is not None and i != block:
+                continue
+            (n_out, k_in), r = L.seg[w][1], L.seg[a][1][0]
+            ops.lora_merge(mp + 4 * L.off(w), mp + 4 * L.off(a), mp + 4 * L.off(b), L.lora_scale, sp + es * L.off(w), None,
+                           int(n_out), int(k_in), int(r))
 
     def mark_shadow_fresh(self):
         self.shadow_version = self.master._version

@@ -426,6 +426,14 @@ class Engine:
         dy.record_stream(side)   # allocated on the main stream: the caching allocator must not hand these
         x.record_stream(side)    # blocks out again before the side stream's reads have finished
 
+    def _lora_grads(self, dy, x, lin, Mtok, N, K, acc, dev):
+        """The gradients of the adapters of linear `lin` from its (dy, x) pair (csrc/lora.hip), on the current stream: the 16-bit
+        adapters come from the shadow, the gradients go to the arena like every other parameter's."""
+        R = self.m.lora_rank
+        ws = self.ws(ops.lora_grads_ws_floats(Mtok, N, K, R), dev)
+        ops.lora_grads(x, dy, self.W(lin + ".lora_A"), self.W(lin + ".lora_B"), self.L.lora_scale, self.G(lin + ".lora_A"),
+                       self.G(lin + ".lora_B"), ws, Mtok, N, K, R, acc)
+
     def WT(self, name):
         """Device address of the transposed 16-bit copy W^T [k_in, n_out] of a block linear's weight (arena.py), or None."""
         if self._shadow_t is None:
@@ -627,6 +635,7 @@ class Engine:
             b = f"blocks.{i}."
             mb = mp + hb * (i * 6 * D)
             last, lin = pl.stage[i], pl.lin[i]   # the stage this block's backward stops behind; which linears want their gradients
+            lora = pl.lora[i] if wgrads else dict.fromkeys(lin, False)   # ... and which linears' adapters
             # MLP branch (its gate backward usually came with the previous LayerNorm backward)
             # (bias gradients of fc2 / proj = column sums of dy2 / dy1: fused into their weight-gradient GEMMs)
             if pre is not None:
@@ -641,6 +650,8 @@ class Engine:
                 wg.append((dy2, bk.u, b + "mlp.fc2.weight", D, Hm))
             elif lin["mlp.fc2"]:
                 self._wgrad(dy2, bk.u, b + "mlp.fc2.weight", M, D, Hm, acc, dev, side=side)
+            if lora["mlp.fc2"]:
+                self._lora_grads(dy2, bk.u, b + "mlp.fc2", M, D, Hm, acc, dev)
             if last >= 2:
                 da1 = bf(M, Hm)
                 self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
@@ -648,6 +659,8 @@ class Engine:
                     wg.append((da1, bk.h2, b + "mlp.fc1.weight", Hm, D))
                 elif lin["mlp.fc1"]:
                     self._wgrad(da1, bk.h2, b + "mlp.fc1.weight", M, Hm, D, acc, dev, side=side)
+                if lora["mlp.fc1"]:
+                    self._lora_grads(da1, bk.h2, b + "mlp.fc1", M, Hm, D, acc, dev)
             if last >= 3:
                 # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
                 dh2 = dy2 if side is None and wg is None else bf(M, D)
@@ -661,6 +674,8 @@ class Engine:
                     wg.append((dy1, bk.o, b + "attn.proj.weight", D, D))
                 elif lin["attn.proj"]:
                     self._wgrad(dy1, bk.o, b + "attn.proj.weight", M, D, D, acc, dev, side=side)
+                if lora["attn.proj"]:
+                    self._lora_grads(dy1, bk.o, b + "attn.proj", M, D, D, acc, dev)
             if last >= 4:
                 do = bf(M, D)
                 dqkv = bf(M, 3 * D)
@@ -692,6 +707,8 @@ class Engine:
                     self._wgrad_block(wg, M, acc, dev, side)
                 elif lin["attn.qkv"]:
                     self._wgrad(dqkv, bk.h, b + "attn.qkv.weight", M, 3 * D, D, acc, dev, side=side)
+                if lora["attn.qkv"]:
+                    self._lora_grads(dqkv, bk.h, b + "attn.qkv", M, 3 * D, D, acc, dev)
             if last >= 5:
                 dh1 = do  # reuse
                 self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)

@@ -6,6 +6,8 @@ forward as one tuple (the signature), and plans once per signature:
     trainable bias, one block's rows of the stacked adaLN GEMM) runs as it does in the fully trainable model, its frozen outputs
     landing in the gradient arena where nothing reads them (p.grad stays None, the optimiser walks the trainable ranges only);
   * the grouped weight-gradient launch serves a block whose four linears all need theirs, the per-GEMM launches the rest;
+  * the adapters of an adapted linear (lora_A / lora_B) take a launch of their own off the linear's (dy, x) pair, beside the base
+    weight's launch or instead of it; they count like the linear itself for stages, truncation and what the forward saves;
   * truncation: with x_embedder, t_embedder, y_embedder and every block below k frozen and no input requiring grad, nothing below
     block k consumes the activation-gradient chain — blocks < k run no backward and save nothing in the forward, the conditioning
     tail is skipped, block k stops at the stage that completes its own gradients, and a projector tap forms its contribution to
@@ -39,8 +41,12 @@ class FreezePlan:
         def on(prefix):
             return prefix + ".weight" in tr or prefix + ".bias" in tr
 
+        def lo(prefix):   # the adapters of an adapted linear (reed_amd/lora.py): their own launch off the linear's (dy, x) pair
+            return prefix + ".lora_A" in tr or prefix + ".lora_B" in tr
+
         # what each launch would write
         self.lin = [{n: on(f"blocks.{i}.{n}") for n in LINEARS} for i in range(depth)]
+        self.lora = [{n: lo(f"blocks.{i}.{n}") for n in LINEARS} for i in range(depth)]
         self.qknorm = [bool(qk_norm) and (on(f"blocks.{i}.attn.q_norm") or on(f"blocks.{i}.attn.k_norm")) for i in range(depth)]
         self.ada = [on(f"blocks.{i}.adaLN_modulation.1") for i in range(depth)] + [on("final_layer.adaLN_modulation.1")]
         self.any_ada = any(self.ada)
@@ -50,7 +56,7 @@ class FreezePlan:
         self.t0, self.t2 = on("t_embedder.mlp.0"), on("t_embedder.mlp.2")
         self.label = "y_embedder.embedding_table.weight" in tr
         self.proj_w = [{k: on(f"projectors.{j}.{k}") for k in PROJ_LAYERS} for j in range(len(tap_depth))]
-        block_on = [any(self.lin[i].values()) or self.qknorm[i] or self.ada[i] for i in range(depth)]
+        block_on = [any(self.lin[i].values()) or any(self.lora[i].values()) or self.qknorm[i] or self.ada[i] for i in range(depth)]
         # the chain runs to the bottom for the patch embedder or dL/dx; the conditioning tail (which reads every block's
         # modulation gradients) for the timestep MLP, the label table or dL/dt
         bottom = self.x_emb or self.need_x
@@ -64,7 +70,8 @@ class FreezePlan:
             self.stage = [0] * self.k + [5] * (depth - self.k)
             if self.k < depth:
                 i = self.k
-                s = max([STAGE_OF[n] for n in LINEARS if self.lin[i][n]] + [4 if self.qknorm[i] else 0, 5 if self.ada[i] else 0])
+                s = max([STAGE_OF[n] for n in LINEARS if self.lin[i][n] or self.lora[i][n]] +
+                        [4 if self.qknorm[i] else 0, 5 if self.ada[i] else 0])
                 self.stage[i] = s
         self.save = [s > 0 for s in self.stage]
         # the final layer: its row kernel for its linear's gradients or the chain; its LayerNorm backward for the chain or its adaLN rows
@@ -107,6 +114,8 @@ class FreezePlan:
             for n in LINEARS:
                 if self.lin[i][n] and STAGE_OF[n] <= self.stage[i]:
                     out.append(f"block{i}.wgrad.{n}")
+                if self.lora[i][n] and STAGE_OF[n] <= self.stage[i]:
+                    out.append(f"block{i}.lora.{n}")
             if self.qknorm[i] and self.stage[i] >= 4:
                 out.append(f"block{i}.qknorm_rowsum")
         for dj in sorted(taps, reverse=True):

@@ -52,9 +52,13 @@ class SiT(nn.Module):
         if decoder_hidden_size != hidden_size:
             raise ValueError(f"decoder_hidden_size ({decoder_hidden_size}) must equal hidden_size ({hidden_size}): "
                              "FinalLayer consumes the last block's tokens (reference sit.py:215,308)")
-        unknown = set(block_kwargs) - {"fused_attn", "qk_norm"}
+        unknown = set(block_kwargs) - {"fused_attn", "qk_norm", "lora_rank", "lora_alpha", "lora_targets"}
         if unknown:
             raise TypeError(f"unexpected block kwargs {sorted(unknown)}")
+        # LoRA (reed_amd/lora.py): adapters lora_A [R, k_in], lora_B [n_out, R] on the named block linears, W' = W + (alpha / R) B A
+        from ..lora import check_config
+        self.lora_rank, self.lora_alpha, self.lora_targets = check_config(
+            block_kwargs.get("lora_rank"), block_kwargs.get("lora_alpha"), block_kwargs.get("lora_targets"))
         self.path_type = path_type
         self.in_channels = in_channels
         self.out_channels = in_channels
@@ -87,10 +91,13 @@ class SiT(nn.Module):
 
         shapes = self._param_shapes()
         self._layout = ArenaLayout(shapes, depth, len(self.z_dims))
+        if self.lora_rank:
+            self._layout.lora_scale = self.lora_alpha / self.lora_rank
         self._arena = ParamArena(self._layout, "cpu")
         self._engine = None
         self._build_tree(shapes)
         self.initialize_weights()
+        self._init_lora()
         self.force_drop_mask = None  # tests: bool [N] replacing LabelEmbedder's torch.rand draw
         # operand type of the kernels = which build of the library evaluates this model (reed_amd/_lib.py): "bf16" (the reference
         # under accelerate bf16), "fp16" (IEEE half: sampling at the mantissa of the reference's TF32, and --mixed-precision fp16
@@ -111,6 +118,12 @@ class SiT(nn.Module):
         D, p, C = self.hidden_size, self.patch_size, self.in_channels
         Hm = int(D * self.mlp_ratio)
         sh = OrderedDict()
+
+        def lora(lin, b, n_out, k_in):   # the adapters of an adapted linear, right behind its bias
+            if self.lora_rank and lin in self.lora_targets:
+                sh[b + lin + ".lora_A"] = (self.lora_rank, k_in)
+                sh[b + lin + ".lora_B"] = (n_out, self.lora_rank)
+
         sh["x_embedder.proj.weight"] = (D, C, p, p)
         sh["x_embedder.proj.bias"] = (D,)
         sh["t_embedder.mlp.0.weight"] = (D, 256)
@@ -123,6 +136,7 @@ class SiT(nn.Module):
             b = f"blocks.{i}."
             sh[b + "attn.qkv.weight"] = (3 * D, D)
             sh[b + "attn.qkv.bias"] = (3 * D,)
+            lora("attn.qkv", b, 3 * D, D)
             if self.qk_norm:  # timm Attention: q_norm / k_norm = LayerNorm(head_dim) between qkv and proj
                 hd = D // self.num_heads
                 for n in ("q_norm", "k_norm"):
@@ -130,10 +144,13 @@ class SiT(nn.Module):
                     sh[b + f"attn.{n}.bias"] = (hd,)
             sh[b + "attn.proj.weight"] = (D, D)
             sh[b + "attn.proj.bias"] = (D,)
+            lora("attn.proj", b, D, D)
             sh[b + "mlp.fc1.weight"] = (Hm, D)
             sh[b + "mlp.fc1.bias"] = (Hm,)
+            lora("mlp.fc1", b, Hm, D)
             sh[b + "mlp.fc2.weight"] = (D, Hm)
             sh[b + "mlp.fc2.bias"] = (D,)
+            lora("mlp.fc2", b, D, Hm)
             sh[b + "adaLN_modulation.1.weight"] = (6 * D, D)
             sh[b + "adaLN_modulation.1.bias"] = (6 * D,)
         P = self.projector_dim
@@ -264,6 +281,20 @@ class SiT(nn.Module):
         for n in ("final_layer.adaLN_modulation.1.weight", "final_layer.adaLN_modulation.1.bias",
                   "final_layer.linear.weight", "final_layer.linear.bias"):
             sd[n].zero_()
+
+    @torch.no_grad()
+    def _init_lora(self):
+        """B = 0, A ~ U(-1 / sqrt(k_in), 1 / sqrt(k_in)), drawn after every draw of initialize_weights (the base weights of a seed
+        are the same with and without adapters); the base weight and bias of an adapted linear start frozen."""
+        if not self.lora_rank:
+            return
+        sd = dict(self.named_parameters())
+        for _, w, a, b in self._layout.lora:
+            k_in = sd[a].shape[1]
+            sd[a].copy_(torch.empty(sd[a].shape).uniform_(-1.0 / math.sqrt(k_in), 1.0 / math.sqrt(k_in)))
+            sd[b].zero_()
+            sd[w].requires_grad_(False)
+            sd[w[:-len("weight")] + "bias"].requires_grad_(False)
 
     # ------------------------------------------------------------------ compute
     def unpatchify(self, x, patch_size=None):

@@ -541,6 +541,30 @@ def cast_bf16(src, dst, n):
     _call("reed_cast_bf16", _p(src), _p(dst), n, _stream())
 
 
+# ---------------- LoRA (csrc/lora.hip) ----------------
+LORA_RANKS = (8, 16, 32, 64)
+LORA_UV_ROWS = 64     # rows of x | dy per workgroup of the u / v pass (16-bit builds): the "row slab" the tests straddle
+LORA_WG_SLABS = 32    # from this many 32-row steps of M on, a slab of the partial-sum pass holds more than one step
+
+
+def lora_merge(w, a, b, scale, w_op, w32, N, K, R):
+    """w' = w + scale * b @ a from the fp32 masters; w_op (operand type) <- r(w') and / or w32 <- w'."""
+    _call("reed_lora_merge", _p(w), _p(a), _p(b), float(scale), _p(w_op), _p(w32), N, K, R, _stream())
+
+
+def lora_grads_ws_floats(M, N, K, R):
+    n = _lib.load(_PRECISION).reed_lora_grads_ws_floats(M, N, K, R)
+    if n < 0:
+        raise ValueError(f"reed_lora_grads: M={M}, N={N}, K={K}, R={R} is outside the kernel's domain ({_PRECISION} build)")
+    return int(n)
+
+
+def lora_grads(x, dy, a16, b16, scale, da, db, ws, M, N, K, R, accumulate=False):
+    """da f32 [R, K] (+)= v^T x, db f32 [N, R] (+)= dy^T u with u = r(scale x a16^T), v = r(scale dy b16)."""
+    _call("reed_lora_grads", _p(x), _p(dy), _p(a16), _p(b16), float(scale), _p(da), _p(db), _p(ws), M, N, K, R, int(accumulate),
+          _stream())
+
+
 # ---------------- attention ----------------
 def attention_fwd(qkv, o, lse, B, T, H, hd):
     _call("reed_attention_fwd", _p(qkv), _p(o), _p(lse), B, T, H, hd, _stream())

@@ -120,7 +120,10 @@ class FusedAdamWEMA:
             else:
                 ops.adamw_ema_ranges(A.master, A.grad, self.exp_avg, self.exp_avg_sq, ema_buf, A.shadow, L.n_train, L.n_total, nc,
                                      self.lr, b1, b2, self.eps, self.weight_decay, bc1, bc2, self.ema_decay, rg, scaler_state=st)
+            A.merge_lora()   # the pass above left r(W) in the shadow of an adapted weight: r(W + s B A) before anyone reads it
         else:
+            if L.lora and self._want_shard:
+                raise RuntimeError("FusedAdamWEMA: REED_OPT_SHARD with LoRA adapters is not implemented; unset REED_OPT_SHARD")
             A.wait_all()
             main = torch.cuda.current_stream()
             if self._stream is None:
@@ -190,6 +193,8 @@ class FusedAdamWEMA:
                             update(b, e)
                         else:
                             update_ranged(name, b, e)
+                        if L.lora and name.startswith("block"):   # behind the block's update, in front of its event
+                            A.merge_lora(int(name[5:]))
                         ev = torch.cuda.Event()
                         ev.record(side)
                         A.pending[name] = ev

@@ -136,12 +136,30 @@ def parse_args(input_args=None):
     parser.add_argument("--init-from", type=str, default=None, metavar="CKPT",
                         help="start at step 0 from the weights of a checkpoint written by this script: loads ckpt['model'] and "
                              "ckpt['ema'], no optimiser state (--resume-step continues a run instead)")
+    parser.add_argument("--lora-rank", type=int, default=0, choices=[0, 8, 16, 32, 64],
+                        help="LoRA fine-tuning (reed_amd/lora.py): adapters of this rank on the block linears named by "
+                             "--lora-targets, W' = W + (alpha / rank) B A; 0 = off.  Alone, only the adapters train; with "
+                             "--train-only the adapters and the matches; --freeze applies as given (what it does not match trains, "
+                             "base weights included).  Meant for --init-from <a pre-trained checkpoint without adapters>; "
+                             "`python -m reed_amd.lora merge` turns the result into a plain checkpoint")
+    parser.add_argument("--lora-alpha", type=float, default=None, help="LoRA alpha (default: the rank, scale 1)")
+    parser.add_argument("--lora-targets", type=str, nargs="+", default=None, metavar="LINEAR",
+                        help="adapted block linears, a subset of attn.qkv attn.proj mlp.fc1 mlp.fc2 (default: all four)")
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft checkpoint (diffusers layout): turns on the reference's preview sampling at step 1 "
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
     if args.init_from and args.resume_step > 0:
         parser.error("--init-from starts a new run at step 0; --resume-step continues one: pass one of the two")
+    if args.lora_rank:
+        from .lora import check_config
+        try:   # args.json holds the resolved values
+            args.lora_rank, args.lora_alpha, targets = check_config(args.lora_rank, args.lora_alpha, args.lora_targets)
+        except ValueError as e:
+            parser.error(str(e))
+        args.lora_targets = list(targets)
+    elif args.lora_alpha is not None or args.lora_targets:
+        parser.error("--lora-alpha / --lora-targets need --lora-rank")
     args.encoder_precision = resolve_encoder_precision(args.encoder_precision, args.mixed_precision)   # args.json holds the result
     args.gemm_tf32 = resolve_tf32(args.allow_tf32, args.mixed_precision)                               # and this one
     if args.encoder_ckpts and args.resolution != 256:
@@ -165,6 +183,32 @@ def apply_freeze(model, freeze=None, train_only=None):
     for n, p in named:
         p.requires_grad_(n in on)
     return sum(p.numel() for n, p in named if n in on)
+
+
+LORA_PATTERNS = ["*.lora_A", "*.lora_B"]
+
+
+def apply_lora_freeze(model, freeze=None, train_only=None):
+    """The trainable set of a model with adapters: --lora-rank alone = the adapters only; with --train-only the adapters and the
+    matches; --freeze as given (everything it does not match trains).  Returns the number of trainable elements."""
+    if freeze:
+        return apply_freeze(model, freeze, None)
+    return apply_freeze(model, None, list(train_only or []) + LORA_PATTERNS)
+
+
+def load_base_state_dict(model, sd, what="--init-from"):
+    """load_state_dict for a model that may carry adapters from a checkpoint that may not: exactly the *.lora_A / *.lora_B keys
+    may be missing (the adapters keep their initial values: B = 0, the loaded model computes what the checkpoint's did); any other
+    missing key, and any unexpected one, is an error."""
+    from .lora import is_adapter_key
+    if not getattr(model, "lora_rank", 0) or any(is_adapter_key(k) for k in sd):
+        return model.load_state_dict(sd)
+    res = model.load_state_dict(sd, strict=False)
+    missing = [k for k in res.missing_keys if not is_adapter_key(k)]
+    if missing or res.unexpected_keys:
+        raise RuntimeError(f"{what}: the checkpoint does not fit the model: missing {missing[:4]}, unexpected "
+                           f"{list(res.unexpected_keys)[:4]} (only *.lora_A / *.lora_B may be missing)")
+    return res
 
 
 def resolve_tf32(allow_tf32, mixed_precision):
@@ -298,10 +342,12 @@ def main(args):
     if args.features_dirs and len(args.features_dirs) != n_img_enc:
         raise ValueError("--features-dirs needs one directory per --enc-type entry")
 
+    lora_rank = getattr(args, "lora_rank", 0)
+    lora_kw = dict(lora_rank=lora_rank, lora_alpha=args.lora_alpha, lora_targets=args.lora_targets) if lora_rank else {}
     model = SiT_models[args.model](input_size=latent_size, num_classes=args.num_classes, use_cfg=(args.cfg_prob > 0),
                                    z_dims=z_dims, z_types=z_types, encoder_depth=args.encoder_depth,
                                    encoder_depth_text=args.encoder_depth_text, fused_attn=args.fused_attn,
-                                   qk_norm=args.qk_norm).to(device)
+                                   qk_norm=args.qk_norm, **lora_kw).to(device)
     # accelerate's mixed_precision (train.py:141-151): "bf16" = bf16 operands (libreed_hip.so); "fp16" (the reference's default
     # and README recipe) = IEEE-half operands (libreed_hip_f16.so) with dynamic loss scaling (GradScaler defaults) in the
     # fused optimiser pass. Master weights, residual stream, LayerNorm, loss and optimiser state are fp32 either way.
@@ -313,7 +359,15 @@ def main(args):
     allow_tf32 = getattr(args, "allow_tf32", False)
     model.tf32 = getattr(args, "gemm_tf32", resolve_tf32(allow_tf32, args.mixed_precision))
     # --freeze / --train-only, before the optimiser is built (it plans its passes from the trainable set)
-    if getattr(args, "freeze", None) or getattr(args, "train_only", None):
+    if lora_rank:
+        n_on = apply_lora_freeze(model, getattr(args, "freeze", None), getattr(args, "train_only", None))
+        logger_msg = (f"--lora-rank {lora_rank} (alpha {model.lora_alpha:g}, {' '.join(model.lora_targets)})"
+                      f"{' --freeze ' + ' '.join(args.freeze) if args.freeze else ''}"
+                      f"{' --train-only ' + ' '.join(args.train_only) if args.train_only else ''}: "
+                      f"{n_on:,} trainable parameters of {sum(p.numel() for p in model.parameters()):,}")
+        if not getattr(args, "init_from", None) and not args.resume_step:
+            logger.warning("--lora-rank without --init-from or --resume-step: the adapters train on a randomly initialised, frozen base")
+    elif getattr(args, "freeze", None) or getattr(args, "train_only", None):
         n_on = apply_freeze(model, args.freeze, args.train_only)
         logger_msg = (f"{'--freeze ' + ' '.join(args.freeze) if args.freeze else '--train-only ' + ' '.join(args.train_only)}: "
                       f"{n_on:,} trainable parameters of {sum(p.numel() for p in model.parameters()):,}")
@@ -390,8 +444,8 @@ def main(args):
         global_step = ckpt["steps"]
     elif getattr(args, "init_from", None):
         ckpt = torch.load(args.init_from, map_location="cpu", weights_only=False)
-        model.load_state_dict(ckpt["model"])
-        ema.load_state_dict(ckpt["ema"])
+        load_base_state_dict(model, ckpt["model"])
+        load_base_state_dict(ema, ckpt["ema"])
         logger.info(f"--init-from {args.init_from}: model and EMA weights of step {ckpt.get('steps', '?')}, a fresh optimiser, step 0")
     reducer = None
     if world > 1:
