@@ -9,6 +9,11 @@ Per block the launch sequence is
   bwd : gate-bwd, 2x{wgrad, dgrad} for the MLP, LN-bwd, gate-bwd, proj {wgrad, dgrad}, attention-bwd,
         qkv {wgrad, dgrad}, LN-bwd, modulation-grad reduce                                (14 launches)
 and the modulation of ALL blocks is one GEMM forward (silu(c) @ W_ada_all^T) and two backward.
+
+Each decision has one site: a block linear's forward launch (16-bit or MX-fp8) is `linear` in Engine._forward, its parameter
+gradients (grouped launch / own launch / adapters, as freeze.py's plan says) are Engine._lin_grads.  The backward runs as phases
+over one per-call record: _backward_final, _backward_block for each block from the top, _backward_tail (adaLN + conditioning),
+_backward_end (the buckets not yet fired, the inputs' gradients, the side stream's join) — full and truncated alike.
 """
 import contextlib
 import logging
@@ -18,11 +23,23 @@ import types
 import torch
 
 from . import ops
-from .freeze import FreezePlan
+from .freeze import LINEARS, FreezePlan
 from .ops import (NT, NN, TN, EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB,
                   EPI_GELU_G, EPI_SILU_G, EPI_MUL)
 
 logger = logging.getLogger(__name__)
+
+
+def _allocators(hdt, dev):
+    """(bf, f32): uninitialised arrays on `dev`, of the build's operand type `hdt` / of fp32."""
+    def bf(*s):
+        return torch.empty(s, dtype=hdt, device=dev)
+
+    def f32(*s):
+        return torch.empty(s, dtype=torch.float32, device=dev)
+
+    return bf, f32
+
 
 class Engine:
     # Kernel forms picked by the token count per GPU (both measured on MI355X with SiT-XL/2; bench.py prints them under
@@ -64,7 +81,7 @@ class Engine:
         self.tap_depth = [model.encoder_depth if (zt == "i" or not split) else model.encoder_depth_text
                           for zt in model.z_types]
         self.reducer = None      # set by reed_amd.parallel.GradReducer
-        self._dot_delta = {}     # (tokens, operand type, reducing, forced tile, CU reserve, comm forms) -> the dO GEMM has the head-dot epilogue
+        self._dot_delta = {}     # (tokens, operand type, reducing, forced tile, CU reserve, comm forms, NT dgrad) -> the dO GEMM has the head-dot epilogue
         self._ws = None
         self._named = None       # [(name, parameter)], cached: named_parameters() walks the module tree
         self._plans = {}         # (requires_grad signature, x needs grad, t needs grad) -> FreezePlan
@@ -143,14 +160,14 @@ class Engine:
         return self._ws_side
 
     # ---- forward -------------------------------------------------------------------
-    FP8_LAYERS = ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")
+    FP8_LAYERS = LINEARS[::-1]   # the block linears in forward order
 
     def fp8_layers(self, tokens=None, precision=None):
         """{block linear: True where it runs on the MX-fp8 GEMM with SiT.fp8 set, False where it stays 16-bit} for a forward of
         `tokens` rows (default: one sample) — what reed_gemm_mxfp8_plan says of each layer's (epilogue, M, N, K), host arithmetic."""
         D, Hm = self.D, self.Hm
         M = int(tokens) if tokens else self.T
-        prec = precision or getattr(self.m, "precision", "bf16")
+        prec = precision or self.m.precision
         if prec not in ("bf16", "fp16"):
             return {n: False for n in self.FP8_LAYERS}
         shapes = {"attn.qkv": (EPI_BF16, 3 * D, D), "attn.proj": (EPI_GATE_RES, D, D), "mlp.fc1": (EPI_GELU, Hm, D),
@@ -160,11 +177,11 @@ class Engine:
     def forward(self, x, t, y, inference, need_grad, drop, plan=None):
         """plan: the FreezePlan of this forward's backward (need_grad only; None = every block saves, as with every parameter
         trainable)."""
-        prec = getattr(self.m, "precision", "bf16")
-        if need_grad and getattr(self.m, "fp8", False):
+        prec = self.m.precision
+        if need_grad and self.m.fp8:
             raise RuntimeError("reed_amd.SiT: fp8 is a sampling mode (inference forward under torch.no_grad()); a forward that "
                                "builds a graph (training, input gradients) needs model.fp8 = False")
-        with ops.build(prec, bool(getattr(self.m, "tf32", False))):
+        with ops.build(prec, bool(self.m.tf32)):
             return self._forward(x, t, y, inference, need_grad, drop, prec, plan)
 
     def _forward(self, x, t, y, inference, need_grad, drop, prec, plan=None):
@@ -188,13 +205,7 @@ class Engine:
         x = x.contiguous().float()
         t = t.contiguous().float()
         y = y.contiguous().long()
-
-        def bf(*s):
-            return torch.empty(s, dtype=hdt, device=dev)
-
-        def f32(*s):
-            return torch.empty(s, dtype=torch.float32, device=dev)
-
+        bf, f32 = _allocators(hdt, dev)
         sag = self.save_act_grad if self.save_act_grad is not None else M > self.SAVE_ACT_GRAD_MIN_TOKENS
         self._sag = sag   # (the projector forward of this call follows it)
         tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, t=t, prec=prec, act_grad=sag, plan=plan) if need_grad else None
@@ -237,6 +248,11 @@ class Engine:
         if pend:
             self.A.wait("ada_head")
         ops.gemm(NT, EPI_BF16, silu_c, sp + hb * L.ada_w_off, B, n_head, D, mod, D, D, Nall, bias=sp + hb * L.ada_b_off)
+
+        def ada_rest():   # the rest of the modulation rows, once the optimiser has rewritten the tail of the adaLN matrix
+            self.A.wait("ada_tail")
+            ops.gemm(NT, EPI_BF16, silu_c, sp + hb * (L.ada_w_off + n_head * D), B, Nall - n_head, D, mp + hb * n_head,
+                     D, D, Nall, bias=sp + hb * (L.ada_b_off + n_head))
         if need_grad:
             tp.sin, tp.t1p, tp.t1, tp.labels_eff, tp.c, tp.silu_c, tp.mod = sin, t1p, t1, labels_eff, c, silu_c, mod
 
@@ -248,7 +264,7 @@ class Engine:
         # on MX-fp8 operands — the activation quantised by a row pass in front of the GEMM, the weight from the arena's quantised
         # copy — each layer decided on its own; everything else, and every other layer, stays on the 16-bit kernels.
         mx_on = ()
-        if not need_grad and prec in ("bf16", "fp16") and getattr(m, "fp8", False):
+        if not need_grad and prec in ("bf16", "fp16") and m.fp8:
             layers = self.fp8_layers(M, prec)
             mx_on = frozenset(n for n, on in layers.items() if on)
             if not self._fp8_logged:
@@ -261,19 +277,27 @@ class Engine:
             aq = torch.empty((M, kmax), dtype=torch.uint8, device=dev)
             asc = torch.empty((M, kmax // ops.MX_BLOCK), dtype=torch.uint8, device=dev)
 
-            def mx_gemm(name, epi, act, N, K, C, ldc, **kw):
+        def linear(lin, epi, act, N, K, C, C2=None, ldc2=0, **kw):
+            """The forward of linear `lin` of the block at hand (b), act [M, K] -> C / C2 [M, N] (+ bias; kw: the epilogue's gate and
+            residual): the MX-fp8 GEMM where fp8 sampling takes this layer (nothing is saved there, and a null output goes with a
+            zero leading dimension), the 16-bit one otherwise."""
+            name = b + lin
+            if lin in mx_on:
                 wq, wsc = mxw[name + ".weight"]
                 ops.mx_quantize(act, aq, asc, M, K)
-                ops.gemm_mxfp8(epi, aq, asc, wq, wsc, M, N, K, C, ldc, bias=self.W(name + ".bias"), **kw)
+                ops.gemm_mxfp8(epi, aq, asc, wq, wsc, M, N, K, C, N if C is not None else 0, C2=C2,
+                               ldc2=ldc2 if C2 is not None else 0, bias=self.W(name + ".bias"), **kw)
+            else:
+                ops.gemm(NT, epi, act, self.W(name + ".weight"), M, N, K, C, K, K, N, C2=C2, ldc2=ldc2,
+                         bias=self.W(name + ".bias"), **kw)
+
         xcur = tok
         zs_by_proj = {}
         for i in range(self.depth):
             b = f"blocks.{i}."
             mb = mp + hb * (i * 6 * D)
             if kh and i == kh:
-                self.A.wait("ada_tail")
-                ops.gemm(NT, EPI_BF16, silu_c, sp + hb * (L.ada_w_off + n_head * D), B, Nall - n_head, D, mp + hb * n_head,
-                         D, D, Nall, bias=sp + hb * (L.ada_b_off + n_head))
+                ada_rest()
                 kh = 0
             if pend:
                 self.A.wait(f"block{i}")
@@ -289,11 +313,7 @@ class Engine:
                 xmid = xb if xcur is xa else xa
                 xout = xcur  # safe: fc2's epilogue reads R=xmid, writes xout; xcur is dead after proj
             ops.ln_modulate_fwd(xcur, mb, mb + hb * D, Nall, h, mean1, rstd1, M, D, T)
-            if "attn.qkv" in mx_on:
-                mx_gemm(b + "attn.qkv", EPI_BF16, h, 3 * D, D, qkv, 3 * D)
-            else:
-                ops.gemm(NT, EPI_BF16, h, self.W(b + "attn.qkv.weight"), M, 3 * D, D, qkv, D, D, 3 * D,
-                         bias=self.W(b + "attn.qkv.bias"))
+            linear("attn.qkv", EPI_BF16, h, 3 * D, D, qkv)
             qkv_a, qstats = qkv, None
             if m.qk_norm:
                 qkv_a = bf(M, 3 * D)
@@ -301,22 +321,12 @@ class Engine:
                 ops.qk_norm_fwd(qkv, self.Wf(b + "attn.q_norm.weight"), self.Wf(b + "attn.q_norm.bias"),
                                 self.Wf(b + "attn.k_norm.weight"), self.Wf(b + "attn.k_norm.bias"), qkv_a, qstats, M, H, hd)
             ops.attention_fwd(qkv_a, o, lse, B, T, H, hd)
-            if "attn.proj" in mx_on:
-                mx_gemm(b + "attn.proj", EPI_GATE_RES, o, D, D, xmid, D, R=xcur, ldr=D, gate=mb + 2 * hb * D, ldgate=Nall, rows_per_gate=T)
-            else:
-                ops.gemm(NT, EPI_GATE_RES, o, self.W(b + "attn.proj.weight"), M, D, D, xmid, D, D, D, C2=y1, ldc2=D,
-                         R=xcur, ldr=D, bias=self.W(b + "attn.proj.bias"), gate=mb + 2 * hb * D, ldgate=Nall, rows_per_gate=T)
+            linear("attn.proj", EPI_GATE_RES, o, D, D, xmid, C2=y1, ldc2=D, R=xcur, ldr=D, gate=mb + 2 * hb * D, ldgate=Nall,
+                   rows_per_gate=T)
             ops.ln_modulate_fwd(xmid, mb + 3 * hb * D, mb + 4 * hb * D, Nall, h2, mean2, rstd2, M, D, T)
-            if "mlp.fc1" in mx_on:
-                mx_gemm(b + "mlp.fc1", EPI_GELU, h2, Hm, D, None, 0, C2=u, ldc2=Hm)
-            else:
-                ops.gemm(NT, epi_gelu if save[i] else EPI_GELU, h2, self.W(b + "mlp.fc1.weight"), M, Hm, D, a1, D, D, Hm, C2=u, ldc2=Hm,
-                         bias=self.W(b + "mlp.fc1.bias"))
-            if "mlp.fc2" in mx_on:
-                mx_gemm(b + "mlp.fc2", EPI_GATE_RES, u, D, Hm, xout, D, R=xmid, ldr=D, gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
-            else:
-                ops.gemm(NT, EPI_GATE_RES, u, self.W(b + "mlp.fc2.weight"), M, D, Hm, xout, Hm, Hm, D, C2=y2, ldc2=D,
-                         R=xmid, ldr=D, bias=self.W(b + "mlp.fc2.bias"), gate=mb + 5 * hb * D, ldgate=Nall, rows_per_gate=T)
+            linear("mlp.fc1", epi_gelu if save[i] else EPI_GELU, h2, Hm, D, a1, C2=u, ldc2=Hm)
+            linear("mlp.fc2", EPI_GATE_RES, u, D, Hm, xout, C2=y2, ldc2=D, R=xmid, ldr=D, gate=mb + 5 * hb * D, ldgate=Nall,
+                   rows_per_gate=T)
             if need_grad and not save[i]:
                 tp.blocks.append(None)
             elif need_grad:
@@ -331,9 +341,7 @@ class Engine:
                         zs_by_proj[j] = self._projector_fwd(j, xcur, B, need_grad and (plan is None or plan.proj[j]["run"]), tp)
         # -- final layer
         if kh:   # depth <= ADA_HEAD_BLOCKS: the tail (final layer's rows) was never launched
-            self.A.wait("ada_tail")
-            ops.gemm(NT, EPI_BF16, silu_c, sp + hb * (L.ada_w_off + n_head * D), B, Nall - n_head, D, mp + hb * n_head,
-                     D, D, Nall, bias=sp + hb * (L.ada_b_off + n_head))
+            ada_rest()
         if pend:
             self.A.wait_all()
         out = f32(B, C, HW, HW)
@@ -364,8 +372,7 @@ class Engine:
         img = m.z_types[j] == "i"
         self.A.wait("projectors")
         R = B * T if img else B
-        hdt = ops.half_dtype()   # the build Engine.forward selected
-        bf = lambda *s: torch.empty(s, dtype=hdt, device=dev)  # noqa: E731
+        bf, _ = _allocators(ops.half_dtype(), dev)   # the build Engine.forward selected
         xin = bf(R, D)
         if img:
             ops.ln_modulate_fwd(x, None, None, 0, xin, None, None, R, D, T)  # f32 -> bf16 cast (autocast input cast)
@@ -413,18 +420,16 @@ class Engine:
         256-row-tile dgrad grid covers 56-84 % of the 256 CUs)."""
         bname = wname.replace("weight", "bias")
         lay, split = ops.plan_wgrad(Mtok, N, K)
-        if side is None:
-            ws = self.ws(split * (N * K + N), dev) if split > 1 else None
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            # (the side stream's split-K slabs are its own: allocated while that stream is current)
+            ws = (self.ws if side is None else self.ws_side)(split * (N * K + N), dev) if split > 1 else None
             ops.linear_wgrad(dy, x, self.G(wname), dbias=None if bias_done else self.G(bname), accumulate=acc,
                              split_k=split, Mtok=Mtok, N=N, K=K, ws=ws, lay=lay)
-            return
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            ws = self.ws_side(split * (N * K + N), dev) if split > 1 else None
-            ops.linear_wgrad(dy, x, self.G(wname), dbias=None if bias_done else self.G(bname), accumulate=acc,
-                             split_k=split, Mtok=Mtok, N=N, K=K, ws=ws, lay=lay)
-        dy.record_stream(side)   # allocated on the main stream: the caching allocator must not hand these
-        x.record_stream(side)    # blocks out again before the side stream's reads have finished
+        if side is not None:
+            dy.record_stream(side)   # allocated on the main stream: the caching allocator must not hand these
+            x.record_stream(side)    # blocks out again before the side stream's reads have finished
 
     def _lora_grads(self, dy, x, lin, Mtok, N, K, acc, dev):
         """The gradients of the adapters of linear `lin` from its (dy, x) pair (csrc/lora.hip), on the current stream: the 16-bit
@@ -456,42 +461,39 @@ class Engine:
         computed only when asked for (need_x / need_t).  frozen: no parameter requires grad — the activation-gradient chain alone
         (the same launches in the same order: dx and dt have the bits of the full backward), no weight or bias gradient, no
         gradient arena."""
-        prec = getattr(self.m, "precision", "bf16")
-        if getattr(tp, "prec", prec) != prec:
+        prec = self.m.precision
+        if tp.prec != prec:
             raise RuntimeError("reed_amd.SiT: model.precision changed between forward and backward")
         if tp.plan is not None and tp.plan.sig != self.signature():
             raise RuntimeError("reed_amd.SiT: a parameter's requires_grad changed between forward and backward; the forward saved "
                                "what the plan of that moment needs (reed_amd/freeze.py). Run the forward again")
         if frozen and self.reducer is not None:
             raise RuntimeError(FROZEN_WITH_REDUCER)
-        prev = ops.use(prec)
-        prev_split = ops.f32_split(bool(getattr(self.m, "tf32", False))) if prec == "fp32" else None
-        # gradient buckets are reduced beside this backward's GEMMs (RCCL channels hold CUs): only then does the library keep to
-        # kernels that degrade gracefully without every CU (csrc/gemm_plan.cpp:reed_set_concurrent_comm); the forward, the
-        # optimiser and the sampler run with no collective in flight (the step waits for the last bucket before the update)
-        comm = self.reducer is not None and self.reducer.active()
-        if comm:
-            ops.set_concurrent_comm(True)
-        try:
-            return self._backward(tp, dout, dzs, ops.half_dtype(prec), need_x, need_t, not frozen)
-        finally:
+        with ops.build(prec, bool(self.m.tf32)):
+            # gradient buckets are reduced beside this backward's GEMMs (RCCL channels hold CUs): only then does the library keep to
+            # kernels that degrade gracefully without every CU (csrc/gemm_plan.cpp:reed_set_concurrent_comm); the forward, the
+            # optimiser and the sampler run with no collective in flight (the step waits for the last bucket before the update)
+            comm = self.reducer is not None and self.reducer.active()
             if comm:
-                ops.set_concurrent_comm(False)
-            if prev_split is not None:
-                ops.f32_split(prev_split)
-            ops.use(prev)
+                ops.set_concurrent_comm(True)
+            try:
+                return self._backward(tp, dout, dzs, need_x, need_t, not frozen)
+            finally:
+                if comm:
+                    ops.set_concurrent_comm(False)
 
-    def _backward(self, tp, dout, dzs, hdt, need_x, need_t, wgrads):
+    def _backward(self, tp, dout, dzs, need_x, need_t, wgrads):
         """wgrads = False (the frozen-weight backward): every launch that only feeds a parameter gradient is skipped; what is
         left runs as it does with them.  In between, the tape's FreezePlan (freeze.py) decides launch by launch, and where the
-        activation-gradient chain stops."""
-        m, L = self.m, self.L
+        activation-gradient chain stops.  The phases, in order: _backward_final, per block from the top down to pl.k the projector
+        taps of its output and _backward_block, _backward_truncated_end (a truncated backward's low projectors), _backward_tail,
+        _backward_end; `s` is the per-call record they share."""
         pl = tp.plan if tp.plan is not None else self.plan_for(need_x, need_t)
-        D, H, hd, Hm, T, P, C = self.D, self.H, self.hd, self.Hm, self.T, self.P, self.C
+        D, H, Hm, T = self.D, self.H, self.Hm, self.T
         B = tp.B
         M = B * T
         dev = dout.device
-        Nall = L.ada_rows
+        hdt = ops.half_dtype(tp.prec)
         hb = self._hb = hdt.itemsize
         if wgrads:
             self.A.ensure_grad()
@@ -499,16 +501,10 @@ class Engine:
         use_t = self.dgrad_nt if self.dgrad_nt is not None else (self.DGRAD_NT_MIN_TOKENS is not None and M >= self.DGRAD_NT_MIN_TOKENS)
         self._shadow_t = self.A.ensure_shadow_t(tp.prec) if (use_t and hb == 2) else None
         acc = self.grad_live
-        mp = tp.mod.data_ptr()
-        ch = T // 16  # 16-row chunks per sample
-
-        def bf(*s):
-            return torch.empty(s, dtype=hdt, device=dev)
-
-        def f32(*s):
-            return torch.empty(s, dtype=torch.float32, device=dev)
-
-        group_wgrad = wgrads and any(pl.group) and ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
+        bf, f32 = _allocators(hdt, dev)
+        red = self.reducer
+        reducing = red is not None and red.active()
+        group = wgrads and any(pl.group) and ops.wgrad_group_fits([(D, Hm), (Hm, D), (D, D), (3 * D, D)])
         nws = ops.attention_bwd_ws_floats(B, T, H)       # delta = rowsum(dO * O) of the persistent attention backward
         attn_ws = f32(nws) if nws else None
         # the answer of the library ("this shape's dO GEMM has the head-dot epilogue") depends on which kernel the GEMM runs on:
@@ -516,243 +512,253 @@ class Engine:
         # keeps off the persistent kernels) and a forced tile — all in the key (a 1002 seen once under one of
         # them was remembered for the rest of the run under the token count alone).
         # (and the CU reserve and the forms-beside-collectives switch, which the tuner cycles under one token count)
-        dkey = (M, str(hdt), self.reducer is not None and self.reducer.active(), ops.gemm_forced_tile(), ops.cu_reserve(),
-                ops.comm_forms())
-        dot_delta = self._dot_delta if self.fused_delta and hdt != torch.float32 else {dkey: False}
+        # (and whether that GEMM is the NT one on the transposed weights or the NN one: two shapes to the planner)
+        dkey = (M, str(hdt), reducing, ops.gemm_forced_tile(), ops.cu_reserve(), ops.comm_forms(), self._shadow_t is not None)
         side = None
         if wgrads and (self.wgrad_stream or (self.wgrad_stream is None and M <= self.wgrad_stream_max_tokens)):
             if self._side is None:
                 self._side = torch.cuda.Stream(device=dev)
             side = self._side
-        dout = dout.contiguous().float()
-        # -- final layer
-        mf = mp + hb * (self.depth * 6 * D)
-        dx = None
-        if pl.final_run:
-            hbuf, dlin, dh = bf(M, D), bf(M, self.NO), bf(M, D)
-            ops.final_layer_bwd_rows(dout, tp.x_last, tp.meanF, tp.rstdF, mf, mf + hb * D, Nall,
-                                     self.W("final_layer.linear.weight"), hbuf, dlin, dh, B, T, D, C, P)
-        if pl.final_ln:
-            dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
-            partF = f32(M // 16, 2, D)
-        # which projectors fire after block i's output?
-        pending = {j: d for j, d in enumerate(self.tap_depth)}
-
-        def tap_fires(depth_idx):   # a projector backward adds into dx at this depth (between block depth_idx-1 and depth_idx)
-            return any(dj == depth_idx and j in tp.proj for j, dj in pending.items())
-
-        def ln_bwd(dh_, x_, mean_, rstd_, scale_ptr, part_, nxt):
-            """LayerNorm+modulate backward into dx. nxt = index of the block whose MLP-branch gate consumes the finished
-            dx next (or None): its gate backward rides along in the same pass unless a projector tap adds into dx in
-            between. Returns (dy2, pg2) of that block when fused."""
-            if nxt is None or nxt < pl.k or tap_fires(nxt + 1):
-                ops.ln_modulate_bwd(dh_, x_, mean_, rstd_, scale_ptr, Nall, dx, part_, M, D, T)
-                return None
-            nb_ = tp.blocks[nxt]
-            dy_, pg_ = bf(M, D), f32(M // 16, D)
-            ops.ln_modulate_bwd_gate(dh_, x_, mean_, rstd_, scale_ptr, Nall, dx, part_, nb_.y2,
-                                     mp + hb * (nxt * 6 * D + 5 * D), Nall, dy_, pg_, None, M, D, T)
-            return dy_, pg_
-
-        pre = ln_bwd(dh, tp.x_last, tp.meanF, tp.rstdF, mf + hb * D, partF, self.depth - 1) if pl.final_ln else None
-        if pl.final_w:
-            wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, C * P * P)), dev)
-            ops.smallk_wgrad(hbuf, False, dlin, wsf, self.G("final_layer.linear.weight"), None,
-                             self.G("final_layer.linear.bias"), M, D, self.NO, 1, acc)
-        # the modulation gradients of every block + the final layer; truncated, only trainable adaLN rows are reduced into it and
-        # the stacked weight-gradient GEMM reads zeros elsewhere
-        dmod = None
-        if pl.dmod:
-            dmod = torch.zeros(B, Nall, dtype=hdt, device=dev) if pl.trunc else bf(B, Nall)
-        offF = self.depth * 6 * D
-        if pl.final_ln and pl.mod_reduce[self.depth]:
-            ops.reduce_mod_parts([(partF.data_ptr(), 2 * D, offF), (partF.data_ptr() + 4 * D, 2 * D, offF + D)], dmod, Nall,
-                                 B, D, ch)
-        if pl.final_run:
-            del hbuf, dlin, dh
         # With a reducer attached the adaLN weight gradient is computed block by block (rows of block i right after
         # block i's backward: dW_ada[i] = dmod[:, i]^T silu(c), a K = b GEMM) instead of one GEMM at the end, so each
         # slice's all-reduce overlaps the rest of backward; the arithmetic per output element is the same.
-        split_ada = pl.any_ada and (self.reducer is not None if self.split_ada_wgrad is None else self.split_ada_wgrad)
-        gp = self.A.grad.data_ptr() if wgrads else None
-        dmp = dmod.data_ptr() if dmod is not None else None
+        split_ada = pl.any_ada and (red is not None if self.split_ada_wgrad is None else self.split_ada_wgrad)
         # Factor path (a reducer that is reducing THIS backward, no gradient accumulation in flight): the adaLN weight
         # gradient contracts over the local batch only, so instead of all-reducing the [Nall, D] fp32 matrix (a third of
         # the payload) the ranks all-gather the two bf16 factors — dmod rows of block i (pre-scaled by 1 / world: exact,
         # power-of-two worlds only) right after block i's backward, silu(c) once — and every rank forms the global-batch
         # product itself at the end of backward (K = world * b). At world = 1 this is the per-block GEMM on a copy.
-        red = self.reducer
-        fg = (red is not None and red.ada_gather and red.active() and not acc and self.split_ada_wgrad is None and wgrads
+        fg = (reducing and red.ada_gather and not acc and self.split_ada_wgrad is None and wgrads
               and not pl.trunc)   # (truncated: the all-reduced per-block slices; the same plan on every rank)
-        if fg:
-            split_ada = False
-            W = red.world
-            g_send, g_recv = red.gather_buffers("dmod", B * Nall, hdt, dev)
-            s_send, s_all = red.gather_buffers("silu", B * D, hdt, dev)
-            s_send.view(B, D).copy_(tp.silu_c)
-            red.gather(s_send, s_all)
-
-        def ada_rows(i):
-            return i * 6 * D, (6 * D if i < self.depth else 2 * D)
-
-        def ada_wgrad(i):
-            c0, rows = ada_rows(i)
-            ops.gemm(TN, EPI_F32, dmp + hb * c0, tp.silu_c, rows, D, B, gp + 4 * (L.ada_w_off + c0 * D), Nall, D, D,
-                     dbias=gp + 4 * (L.ada_b_off + c0), accumulate=acc)
-
-        def ada_gather(i):   # block i's dmod rows are final: scale, pack [b, rows] contiguously, all-gather
-            c0, rows = ada_rows(i)
-            snd = g_send[B * c0:B * (c0 + rows)]
-            torch.mul(dmod[:, c0:c0 + rows], 1.0 / W, out=snd.view(B, rows))
-            red.gather(snd, g_recv[W * B * c0:W * B * (c0 + rows)])
-
-        def ada_after(i):
-            if fg:
-                ada_gather(i)
-            elif split_ada and pl.ada[i]:
-                ada_wgrad(i)
-
-        ada_after(self.depth)
-        if self.reducer is not None:
-            self.reducer.ready("final")
-            if split_ada:
-                self.reducer.ready(f"ada{self.depth}")
-        proj_left = len([j for j in pending if j in tp.proj])
+        dz = {j: dzs[k] for k, j in enumerate(tp.zs_order)} if dzs is not None else {}
+        s = types.SimpleNamespace(tp=tp, pl=pl, wgrads=wgrads, acc=acc, side=side, dev=dev, bf=bf, f32=f32, B=B, M=M, hb=hb,
+                                  Nall=self.L.ada_rows, mp=tp.mod.data_ptr(), group=group, attn_ws=attn_ws, dkey=dkey,
+                                  dot_delta=self._dot_delta if self.fused_delta and hdt != torch.float32 else {dkey: False},
+                                  fg=fg, split_ada=split_ada and not fg, gp=self.A.grad.data_ptr() if wgrads else None, dz=dz,
+                                  dx=None, dmod=None, pre=None, g_send=None, g_recv=None, s_all=None)
+        self._backward_final(s, dout.contiguous().float())
+        proj_left = len(tp.proj)
         proj_fired = False
-        dz_by_proj = {}
-        if dzs is not None:
-            for k, j in enumerate(tp.zs_order):
-                dz_by_proj[j] = dzs[k]
         for i in reversed(range(pl.k, self.depth)):
-            for j, dj in pending.items():
+            for j, dj in enumerate(self.tap_depth):   # which projectors fire after block i's output?
                 if dj == i + 1 and j in tp.proj:
-                    self._projector_bwd(j, tp, dz_by_proj.get(j), dx, B, acc, dev, pl.proj[j])
+                    self._projector_bwd(j, tp, dz.get(j), s.dx, B, acc, dev, pl.proj[j])
                     proj_left -= 1
-                    if proj_left == 0 and self.reducer is not None:
-                        self.reducer.ready("projectors")
+                    if proj_left == 0 and red is not None:
+                        red.ready("projectors")
                         proj_fired = True
-            bk = tp.blocks[i]
-            b = f"blocks.{i}."
-            mb = mp + hb * (i * 6 * D)
-            last, lin = pl.stage[i], pl.lin[i]   # the stage this block's backward stops behind; which linears want their gradients
-            lora = pl.lora[i] if wgrads else dict.fromkeys(lin, False)   # ... and which linears' adapters
-            # MLP branch (its gate backward usually came with the previous LayerNorm backward)
-            # (bias gradients of fc2 / proj = column sums of dy2 / dy1: fused into their weight-gradient GEMMs)
-            if pre is not None:
-                dy2, pg2 = pre
-            else:
-                pg2, dy2 = f32(M // 16, D), bf(M, D)
-                ops.gate_bwd(dx, bk.y2, mb + 5 * hb * D, Nall, dy2, pg2, M, D, T)
-            pre = None
-            # the block's four weight gradients: one launch at the end of the block where all four are wanted
-            wg = [] if group_wgrad and pl.group[i] else None
-            if wg is not None:
-                wg.append((dy2, bk.u, b + "mlp.fc2.weight", D, Hm))
-            elif lin["mlp.fc2"]:
-                self._wgrad(dy2, bk.u, b + "mlp.fc2.weight", M, D, Hm, acc, dev, side=side)
-            if lora["mlp.fc2"]:
-                self._lora_grads(dy2, bk.u, b + "mlp.fc2", M, D, Hm, acc, dev)
-            if last >= 2:
-                da1 = bf(M, Hm)
-                self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
-                if wg is not None:
-                    wg.append((da1, bk.h2, b + "mlp.fc1.weight", Hm, D))
-                elif lin["mlp.fc1"]:
-                    self._wgrad(da1, bk.h2, b + "mlp.fc1.weight", M, Hm, D, acc, dev, side=side)
-                if lora["mlp.fc1"]:
-                    self._lora_grads(da1, bk.h2, b + "mlp.fc1", M, Hm, D, acc, dev)
-            if last >= 3:
-                # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
-                dh2 = dy2 if side is None and wg is None else bf(M, D)
-                self._dgrad(EPI_BF16, da1, b + "mlp.fc1.weight", M, Hm, D, dh2)
-                # LN2 backward + the attention branch's gate backward in one pass over dx
-                pl2 = f32(M // 16, 2, D)
-                pg1, dy1 = f32(M // 16, D), bf(M, D)
-                ops.ln_modulate_bwd_gate(dh2, bk.xmid, bk.mean2, bk.rstd2, mb + 4 * hb * D, Nall, dx, pl2, bk.y1, mb + 2 * hb * D, Nall,
-                                         dy1, pg1, None, M, D, T)
-                if wg is not None:
-                    wg.append((dy1, bk.o, b + "attn.proj.weight", D, D))
-                elif lin["attn.proj"]:
-                    self._wgrad(dy1, bk.o, b + "attn.proj.weight", M, D, D, acc, dev, side=side)
-                if lora["attn.proj"]:
-                    self._lora_grads(dy1, bk.o, b + "attn.proj", M, D, D, acc, dev)
-            if last >= 4:
-                do = bf(M, D)
-                dqkv = bf(M, 3 * D)
-                # delta = rowsum(dO * O) of the attention backward where dO is produced: the GEMM's epilogue 13 leaves per-row,
-                # per-head partial dot products with O (12 MB instead of a 302 MB row pass over dO and O at b = 256); where this
-                # shape's GEMM kernel has no such epilogue (False, decided once per token count) the plain store + the row kernel
-                fused = False
-                if dot_delta.get(dkey, True) and attn_ws is not None:
-                    dpart = f32(M * H * (1 if hd == 64 else 2))
-                    fused = dot_delta[dkey] = ops.dgrad_with_head_dots(dy1, self.W(b + "attn.proj.weight"), do, bk.o, dpart, M, D, D, hd,
-                                                                       wt=self.WT(b + "attn.proj.weight"))
-                if fused:
-                    ops.attention_bwd_dp(bk.qkv_a, do, bk.lse, dpart, dqkv, attn_ws, B, T, H, hd)
-                else:
-                    self._dgrad(EPI_BF16, dy1, b + "attn.proj.weight", M, D, D, do)
-                    ops.attention_bwd(bk.qkv_a, bk.o, do, bk.lse, dqkv, B, T, H, hd, ws=attn_ws)
-                if m.qk_norm:  # back through the per-head LayerNorm of q and k; parameter grads via per-block partials
-                    nb = (M * 3 * H + 255) // 256
-                    part = f32(nb, 4 * hd)
-                    dpre = bf(M, 3 * D)
-                    ops.qk_norm_bwd(dqkv, bk.qkv, bk.qstats, self.Wf(b + "attn.q_norm.weight"),
-                                    self.Wf(b + "attn.k_norm.weight"), dpre, part, M, H, hd)
-                    if pl.qknorm[i]:
-                        ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, acc,
-                                       ws=self.ws((nb + 63) // 64 * 4 * hd, dev))
-                    dqkv = dpre
-                if wg is not None:
-                    wg.append((dqkv, bk.h, b + "attn.qkv.weight", 3 * D, D))
-                    self._wgrad_block(wg, M, acc, dev, side)
-                elif lin["attn.qkv"]:
-                    self._wgrad(dqkv, bk.h, b + "attn.qkv.weight", M, 3 * D, D, acc, dev, side=side)
-                if lora["attn.qkv"]:
-                    self._lora_grads(dqkv, bk.h, b + "attn.qkv", M, 3 * D, D, acc, dev)
-            if last >= 5:
-                dh1 = do  # reuse
-                self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)
-                pl1 = f32(M // 16, 2, D)
-                pre = ln_bwd(dh1, bk.x, bk.mean1, bk.rstd1, mb + hb * D, pl1, i - 1)
-                if pl.mod_reduce[i]:
-                    o6 = i * 6 * D
-                    p1, p2 = pl1.data_ptr(), pl2.data_ptr()
-                    ops.reduce_mod_parts([(p1, 2 * D, o6), (p1 + 4 * D, 2 * D, o6 + D), (pg1.data_ptr(), D, o6 + 2 * D),
-                                          (p2, 2 * D, o6 + 3 * D), (p2 + 4 * D, 2 * D, o6 + 4 * D),
-                                          (pg2.data_ptr(), D, o6 + 5 * D)], dmod, Nall, B, D, ch)
-            tp.blocks[i] = None  # free this block's activations
-            ada_after(i)
-            if self.reducer is not None:
-                if side is None:
-                    self.reducer.ready(f"block{i}")
-                    if split_ada:
-                        self.reducer.ready(f"ada{i}")
-                else:  # the bucket holds gradients written on both streams: fire it from the side stream, after main
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        self.reducer.ready(f"block{i}")
-                        if split_ada:
-                            self.reducer.ready(f"ada{i}")
+            self._backward_block(s, i)
         if pl.trunc:
-            return self._backward_truncated_end(tp, pl, pending, dz_by_proj, proj_fired, B, acc, dev, side, split_ada, dmod, gp)
-        if proj_left > 0 and m.z_dims and self.reducer is not None:   # projector outputs unused by the loss
-            self.reducer.ready("projectors")
-        # -- adaLN (all blocks + final): dW = dmod^T silu(c); d silu(c) = dmod @ W   (one GEMM each)
-        sp = self._shadow.data_ptr()
-        if fg:
-            red.gather_sync()
+            self._backward_truncated_end(s)
+        return self._backward_end(s, self._backward_tail(s), proj_fired, need_x, need_t)
+
+    def _ln_bwd(self, s, dh, x, mean, rstd, scale_ptr, part, nxt):
+        """LayerNorm+modulate backward into dx. nxt = index of the block whose MLP-branch gate consumes the finished
+        dx next: its gate backward rides along in the same pass unless that block does not run or a projector tap adds
+        into dx in between (a projector backward adds into dx between block nxt and nxt + 1). Returns (dy2, pg2) of that block
+        when fused."""
+        tp, M, D, T, Nall = s.tp, s.M, self.D, self.T, s.Nall
+        if nxt < s.pl.k or any(dj == nxt + 1 and j in tp.proj for j, dj in enumerate(self.tap_depth)):
+            ops.ln_modulate_bwd(dh, x, mean, rstd, scale_ptr, Nall, s.dx, part, M, D, T)
+            return None
+        dy, pg = s.bf(M, D), s.f32(M // 16, D)
+        ops.ln_modulate_bwd_gate(dh, x, mean, rstd, scale_ptr, Nall, s.dx, part, tp.blocks[nxt].y2,
+                                 s.mp + s.hb * (nxt * 6 * D + 5 * D), Nall, dy, pg, None, M, D, T)
+        return dy, pg
+
+    def _ada_rows(self, i):
+        """(first row, rows) of block i's part of the stacked adaLN matrix; i = depth: the final layer's."""
+        return i * 6 * self.D, (6 * self.D if i < self.depth else 2 * self.D)
+
+    def _ada_after(self, s, i):
+        """Block i's dmod rows are final: on the factor path scale them, pack them [b, rows] contiguously and all-gather; with the
+        adaLN weight gradient block by block, its rows' GEMM where they are trainable."""
+        if not (s.fg or (s.split_ada and s.pl.ada[i])):
+            return
+        L, D, B = self.L, self.D, s.B
+        c0, rows = self._ada_rows(i)
+        if s.fg:
+            W = self.reducer.world
+            snd = s.g_send[B * c0:B * (c0 + rows)]
+            torch.mul(s.dmod[:, c0:c0 + rows], 1.0 / W, out=snd.view(B, rows))
+            self.reducer.gather(snd, s.g_recv[W * B * c0:W * B * (c0 + rows)])
+        else:
+            ops.gemm(TN, EPI_F32, s.dmod.data_ptr() + s.hb * c0, s.tp.silu_c, rows, D, B, s.gp + 4 * (L.ada_w_off + c0 * D),
+                     s.Nall, D, D, dbias=s.gp + 4 * (L.ada_b_off + c0), accumulate=s.acc)
+
+    def _fire(self, s, name, i, side=None):
+        """Hand gradient bucket `name` to the reducer and, where the adaLN weight gradient goes block by block, ada{i} with it.
+        side: the bucket holds gradients written on both streams: fire it from the side stream, after main."""
+        red = self.reducer
+        if red is None:
+            return
+        if side is not None:
+            side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            red.ready(name)
+            if s.split_ada:
+                red.ready(f"ada{i}")
+
+    def _backward_final(self, s, dout):
+        """The final layer: its row kernel, its LayerNorm backward — which starts dx, the gradient of the residual stream — and its
+        linear's gradients; the modulation gradients' array with the final layer's rows, and the first buckets."""
+        tp, pl, bf, f32 = s.tp, s.pl, s.bf, s.f32
+        D, T, P, C, depth = self.D, self.T, self.P, self.C, self.depth
+        B, M, hb, Nall, dev = s.B, s.M, s.hb, s.Nall, s.dev
+        mf = s.mp + hb * (depth * 6 * D)
+        if pl.final_run:
+            hbuf, dlin, dh = bf(M, D), bf(M, self.NO), bf(M, D)
+            ops.final_layer_bwd_rows(dout, tp.x_last, tp.meanF, tp.rstdF, mf, mf + hb * D, Nall,
+                                     self.W("final_layer.linear.weight"), hbuf, dlin, dh, B, T, D, C, P)
+        if pl.final_ln:
+            s.dx = torch.zeros(M, D, dtype=torch.float32, device=dev)
+            partF = f32(M // 16, 2, D)
+            s.pre = self._ln_bwd(s, dh, tp.x_last, tp.meanF, tp.rstdF, mf + hb * D, partF, depth - 1)
+        if pl.final_w:
+            wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, C * P * P)), dev)
+            ops.smallk_wgrad(hbuf, False, dlin, wsf, self.G("final_layer.linear.weight"), None,
+                             self.G("final_layer.linear.bias"), M, D, self.NO, 1, s.acc)
+        # the modulation gradients of every block + the final layer; truncated, only trainable adaLN rows are reduced into it and
+        # the stacked weight-gradient GEMM reads zeros elsewhere
+        if pl.dmod:
+            s.dmod = torch.zeros(B, Nall, dtype=tp.mod.dtype, device=dev) if pl.trunc else bf(B, Nall)
+        offF = depth * 6 * D
+        if pl.final_ln and pl.mod_reduce[depth]:
+            ops.reduce_mod_parts([(partF.data_ptr(), 2 * D, offF), (partF.data_ptr() + 4 * D, 2 * D, offF + D)], s.dmod, Nall,
+                                 B, D, T // 16)
+        if pl.final_run:
+            del hbuf, dlin, dh
+        if s.fg:
+            red = self.reducer
+            s.g_send, s.g_recv = red.gather_buffers("dmod", B * Nall, tp.mod.dtype, dev)
+            s_send, s.s_all = red.gather_buffers("silu", B * D, tp.mod.dtype, dev)
+            s_send.view(B, D).copy_(tp.silu_c)
+            red.gather(s_send, s.s_all)
+        self._ada_after(s, depth)
+        self._fire(s, "final", depth)
+
+    def _lin_grads(self, s, i, wg, lin, dy, x, N, K):
+        """The parameter gradients of linear `lin` of block i from its (dy, x) pair, as the plan says (freeze.py: group / lin /
+        lora): the weight and bias gradient joins the block's one launch (wg: it goes out with the last linear) or takes a launch
+        of its own; the adapters' gradients follow.
+        (bias gradients of fc2 / proj = column sums of dy2 / dy1: fused into their weight-gradient GEMMs)"""
+        name = f"blocks.{i}.{lin}"
+        if wg is not None:
+            wg.append((dy, x, name + ".weight", N, K))
+            if lin == LINEARS[-1]:
+                self._wgrad_block(wg, s.M, s.acc, s.dev, s.side)
+        elif s.pl.lin[i][lin]:
+            self._wgrad(dy, x, name + ".weight", s.M, N, K, s.acc, s.dev, side=s.side)
+        if s.wgrads and s.pl.lora[i][lin]:
+            self._lora_grads(dy, x, name, s.M, N, K, s.acc, s.dev)
+
+    def _backward_block(self, s, i):
+        """Block i's backward: stages 1 .. pl.stage[i] of freeze.py, then its adaLN rows and its gradient bucket."""
+        tp, pl, bf, f32 = s.tp, s.pl, s.bf, s.f32
+        D, H, hd, Hm, T = self.D, self.H, self.hd, self.Hm, self.T
+        B, M, hb, Nall, dx, side = s.B, s.M, s.hb, s.Nall, s.dx, s.side
+        bk = tp.blocks[i]
+        b = f"blocks.{i}."
+        mb = s.mp + hb * (i * 6 * D)
+        last = pl.stage[i]   # the stage this block's backward stops behind
+        # MLP branch (its gate backward usually came with the previous LayerNorm backward)
+        if s.pre is not None:
+            dy2, pg2 = s.pre
+        else:
+            pg2, dy2 = f32(M // 16, D), bf(M, D)
+            ops.gate_bwd(dx, bk.y2, mb + 5 * hb * D, Nall, dy2, pg2, M, D, T)
+        s.pre = None
+        # the block's four weight gradients: one launch at the end of the block where all four are wanted
+        wg = [] if s.group and pl.group[i] else None
+        self._lin_grads(s, i, wg, "mlp.fc2", dy2, bk.u, D, Hm)
+        if last >= 2:
+            da1 = bf(M, Hm)
+            self._dgrad(EPI_MUL if tp.act_grad else EPI_DGELU, dy2, b + "mlp.fc2.weight", M, D, Hm, da1, R=bk.a1, ldr=Hm)
+            self._lin_grads(s, i, wg, "mlp.fc1", da1, bk.h2, Hm, D)
+        if last >= 3:
+            # reuse dy2 unless its weight gradient (side stream / grouped launch) may still have to read it
+            dh2 = dy2 if side is None and wg is None else bf(M, D)
+            self._dgrad(EPI_BF16, da1, b + "mlp.fc1.weight", M, Hm, D, dh2)
+            # LN2 backward + the attention branch's gate backward in one pass over dx
+            pl2 = f32(M // 16, 2, D)
+            pg1, dy1 = f32(M // 16, D), bf(M, D)
+            ops.ln_modulate_bwd_gate(dh2, bk.xmid, bk.mean2, bk.rstd2, mb + 4 * hb * D, Nall, dx, pl2, bk.y1, mb + 2 * hb * D, Nall,
+                                     dy1, pg1, None, M, D, T)
+            self._lin_grads(s, i, wg, "attn.proj", dy1, bk.o, D, D)
+        if last >= 4:
+            do = bf(M, D)
+            dqkv = bf(M, 3 * D)
+            # delta = rowsum(dO * O) of the attention backward where dO is produced: the GEMM's epilogue 13 leaves per-row,
+            # per-head partial dot products with O (12 MB instead of a 302 MB row pass over dO and O at b = 256); where this
+            # shape's GEMM kernel has no such epilogue (False, decided once per token count) the plain store + the row kernel
+            fused = False
+            if s.dot_delta.get(s.dkey, True) and s.attn_ws is not None:
+                dpart = f32(M * H * (1 if hd == 64 else 2))
+                fused = s.dot_delta[s.dkey] = ops.dgrad_with_head_dots(dy1, self.W(b + "attn.proj.weight"), do, bk.o, dpart, M, D, D,
+                                                                       hd, wt=self.WT(b + "attn.proj.weight"))
+            if fused:
+                ops.attention_bwd_dp(bk.qkv_a, do, bk.lse, dpart, dqkv, s.attn_ws, B, T, H, hd)
+            else:
+                self._dgrad(EPI_BF16, dy1, b + "attn.proj.weight", M, D, D, do)
+                ops.attention_bwd(bk.qkv_a, bk.o, do, bk.lse, dqkv, B, T, H, hd, ws=s.attn_ws)
+            if self.m.qk_norm:  # back through the per-head LayerNorm of q and k; parameter grads via per-block partials
+                nb = (M * 3 * H + 255) // 256
+                part = f32(nb, 4 * hd)
+                dpre = bf(M, 3 * D)
+                ops.qk_norm_bwd(dqkv, bk.qkv, bk.qstats, self.Wf(b + "attn.q_norm.weight"),
+                                self.Wf(b + "attn.k_norm.weight"), dpre, part, M, H, hd)
+                if pl.qknorm[i]:
+                    ops.rowsum_f32(part, nb, self.G(b + "attn.q_norm.weight"), 4 * hd, s.acc,
+                                   ws=self.ws((nb + 63) // 64 * 4 * hd, s.dev))
+                dqkv = dpre
+            self._lin_grads(s, i, wg, "attn.qkv", dqkv, bk.h, 3 * D, D)
+        if last >= 5:
+            dh1 = do  # reuse
+            self._dgrad(EPI_BF16, dqkv, b + "attn.qkv.weight", M, 3 * D, D, dh1)
+            pl1 = f32(M // 16, 2, D)
+            s.pre = self._ln_bwd(s, dh1, bk.x, bk.mean1, bk.rstd1, mb + hb * D, pl1, i - 1)
+            if pl.mod_reduce[i]:
+                o6 = i * 6 * D
+                p1, p2 = pl1.data_ptr(), pl2.data_ptr()
+                ops.reduce_mod_parts([(p1, 2 * D, o6), (p1 + 4 * D, 2 * D, o6 + D), (pg1.data_ptr(), D, o6 + 2 * D),
+                                      (p2, 2 * D, o6 + 3 * D), (p2 + 4 * D, 2 * D, o6 + 4 * D),
+                                      (pg2.data_ptr(), D, o6 + 5 * D)], s.dmod, Nall, B, D, T // 16)
+        tp.blocks[i] = None  # free this block's activations
+        self._ada_after(s, i)
+        self._fire(s, f"block{i}", i, side)
+
+    def _backward_truncated_end(self, s):
+        """What only a truncated backward (FreezePlan.trunc) has: the projector chains whose tap lies at or below the lowest block
+        that ran (weight gradients only: nothing consumes their dx)."""
+        for j, dj in sorted(enumerate(self.tap_depth), key=lambda it: -it[1]):
+            if dj <= s.pl.k and s.tp.proj.get(j) is not None:
+                self._projector_bwd(j, s.tp, s.dz.get(j), None, s.B, s.acc, s.dev, s.pl.proj[j])
+
+    def _backward_tail(self, s):
+        """adaLN (all blocks + final): dW = dmod^T silu(c) — unless it went block by block — and, where the chain runs on
+        (not truncated), d silu(c) = dmod @ W (one GEMM each), the conditioning (label table + timestep MLP) and the patch
+        embedder.  Returns dt1, the gradient at the timestep MLP's first layer (None: truncated)."""
+        tp, pl, L, bf, f32 = s.tp, s.pl, self.L, s.bf, s.f32
+        D, P, C = self.D, self.P, self.C
+        B, M, hb, Nall, acc, dev, gp, dmod = s.B, s.M, s.hb, s.Nall, s.acc, s.dev, s.gp, s.dmod
+        if s.fg:
+            self.reducer.gather_sync()
+            W = self.reducer.world
             for i in reversed(range(self.depth + 1)):   # rank-major [world * b, rows] factors: K = the global batch
-                c0, rows = ada_rows(i)
-                ops.gemm(TN, EPI_F32, g_recv.data_ptr() + hb * W * B * c0, s_all, rows, D, W * B,
+                c0, rows = self._ada_rows(i)
+                ops.gemm(TN, EPI_F32, s.g_recv.data_ptr() + hb * W * B * c0, s.s_all, rows, D, W * B,
                          gp + 4 * (L.ada_w_off + c0 * D), rows, D, D, dbias=gp + 4 * (L.ada_b_off + c0), accumulate=False)
-        elif pl.any_ada and not split_ada:
+        elif pl.any_ada and not s.split_ada:
             ops.gemm(TN, EPI_F32, dmod, tp.silu_c, Nall, D, B, gp + 4 * L.ada_w_off, Nall, D, D,
                      dbias=gp + 4 * L.ada_b_off, accumulate=acc)
+        if pl.trunc:
+            return None
         ksteps = Nall // 64
         split = min(64, max(1, ksteps // 8))
         slab = B * D
         wsd = self.ws(split * slab, dev)
-        ops.gemm(NN, EPI_F32, dmod, sp + hb * L.ada_w_off, B, D, Nall, wsd, Nall, D, D, split_k=split, slab_stride=slab)
+        ops.gemm(NN, EPI_F32, dmod, self._shadow.data_ptr() + hb * L.ada_w_off, B, D, Nall, wsd, Nall, D, D, split_k=split,
+                 slab_stride=slab)
         per = (ksteps + split - 1) // split
         eff = (ksteps + per - 1) // per
         dsilu = f32(B, D)
@@ -779,63 +785,49 @@ class Engine:
             xb = bf(M, K)
             ops.patchify_bf16(tp.x, xb, B, C, tp.x.shape[-1], P, 0)
             wsf = self.ws(ops.smallk_ws_floats(D, max(self.NO, K)), dev)
-            ops.smallk_wgrad(dx, True, xb, wsf, self.G("x_embedder.proj.weight"), self.G("x_embedder.proj.bias"), None, M, D,
+            ops.smallk_wgrad(s.dx, True, xb, wsf, self.G("x_embedder.proj.weight"), self.G("x_embedder.proj.bias"), None, M, D,
                              K, 0, acc)
-        if self.reducer is not None:
-            if fg:   # adaLN weights and biases are global-batch averages already: reduce only the embedders' part
-                eb, ee = self.reducer.buckets["embed"]
-                self.reducer.ready_range(L.ada_b_off + Nall, ee)
-            else:
-                if not split_ada:
-                    for i in reversed(range(self.depth + 1)):
-                        self.reducer.ready(f"ada{i}")
-                self.reducer.ready("embed")
-        # -- the inputs' gradients, after everything they depend on: dL/dt through the sinusoid from dsin = dt1 @ W0 (fp32 out: not
-        # rounded again), dL/dx = the convolution's input gradient of the finished token gradient
+        return dt1
+
+    def _backward_inputs(self, s, dt1, need_x, need_t):
+        """The inputs' gradients, after everything they depend on: dL/dt through the sinusoid from dsin = dt1 @ W0 (fp32 out: not
+        rounded again), dL/dx = the convolution's input gradient of the finished token gradient."""
+        tp, B, D = s.tp, s.B, self.D
         dt_in = dx_in = None
         if need_t:
-            dsin = f32(B, 256)
+            dsin = s.f32(B, 256)
             ops.gemm(NN, EPI_F32, dt1, self.W("t_embedder.mlp.0.weight"), B, 256, D, dsin, D, 256, 256)
-            dt_in = f32(B)
+            dt_in = s.f32(B)
             ops.timestep_sinusoid_bwd(tp.t, dsin, dt_in, B)
         if need_x:
             dx_in = torch.empty_like(tp.x)
-            ops.patch_embed_bwd_x(dx, self.W("x_embedder.proj.weight"), dx_in, B, C, tp.x.shape[-1], P, D)
-        if side is not None:  # the optimiser / next micro-step (same stream as this backward) sees every weight gradient
-            torch.cuda.current_stream().wait_stream(side)
-        if wgrads:
-            self.grad_live = True
-            self._attach_grads()
+            ops.patch_embed_bwd_x(s.dx, self.W("x_embedder.proj.weight"), dx_in, B, self.C, tp.x.shape[-1], self.P, D)
         return dx_in, dt_in
 
-    def _backward_truncated_end(self, tp, pl, pending, dz_by_proj, proj_fired, B, acc, dev, side, split_ada, dmod, gp):
-        """The end of a truncated backward (FreezePlan.trunc): the projector chains whose tap lies at or below the lowest block that
-        ran (weight gradients only: nothing consumes their dx), the stacked adaLN weight gradient where no reducer takes it in
-        slices, and every gradient bucket that has not fired yet, in the fixed order of the full backward."""
-        L, D = self.L, self.D
-        for j, dj in sorted(pending.items(), key=lambda it: -it[1]):
-            if dj <= pl.k and j in tp.proj and tp.proj[j] is not None:
-                self._projector_bwd(j, tp, dz_by_proj.get(j), None, B, acc, dev, pl.proj[j])
-        if pl.any_ada and not split_ada:
-            Nall = L.ada_rows
-            ops.gemm(TN, EPI_F32, dmod, tp.silu_c, Nall, D, B, gp + 4 * L.ada_w_off, Nall, D, D,
-                     dbias=gp + 4 * L.ada_b_off, accumulate=acc)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        if self.reducer is not None:
-            for i in reversed(range(pl.k)):
-                self.reducer.ready(f"block{i}")
-                if split_ada:
-                    self.reducer.ready(f"ada{i}")
-            if self.m.z_dims and not proj_fired and hasattr(tp, "zs_order"):
-                self.reducer.ready("projectors")
-            if not split_ada:
-                for i in reversed(range(self.depth + 1)):
-                    self.reducer.ready(f"ada{i}")
-            self.reducer.ready("embed")
-        self.grad_live = True
-        self._attach_grads()
-        return None, None
+    def _backward_end(self, s, dt1, proj_fired, need_x, need_t):
+        """The one end of every backward: the gradient buckets nothing has fired yet, in the reducer's fixed order (the blocks
+        below a truncated backward, the projectors where the loop did not reach the last of them, the adaLN slices unless they
+        went block by block, the embedders), the inputs' gradients, the side stream's join; returns (dL/dx, dL/dt)."""
+        red = self.reducer
+        if red is not None:
+            for i in reversed(range(s.pl.k)):
+                self._fire(s, f"block{i}", i)
+            if self.m.z_dims and not proj_fired and hasattr(s.tp, "zs_order"):
+                red.ready("projectors")
+            if s.fg:   # adaLN weights and biases are global-batch averages already: reduce only the embedders' part
+                red.ready_range(self.L.ada_b_off + s.Nall, red.buckets["embed"][1])
+            else:
+                if not s.split_ada:
+                    for i in reversed(range(self.depth + 1)):
+                        red.ready(f"ada{i}")
+                red.ready("embed")
+        grads = self._backward_inputs(s, dt1, need_x, need_t)
+        if s.side is not None:  # the optimiser / next micro-step (same stream as this backward) sees every weight gradient
+            torch.cuda.current_stream().wait_stream(s.side)
+        if s.wgrads:
+            self.grad_live = True
+            self._attach_grads()
+        return grads
 
     def _projector_bwd(self, j, tp, dz, dx, B, acc, dev, pj=None):
         """pj: the plan's entry for this projector (freeze.py) — which layers want their weight gradient, the layer the chain
@@ -857,7 +849,7 @@ class Engine:
         if dz.dtype != hdt:
             dz = dz.to(hdt)
         dz = dz.contiguous()
-        bf = lambda *s: torch.empty(s, dtype=hdt, device=dev)  # noqa: E731
+        bf, _ = _allocators(hdt, dev)
         tp.proj[j] = None
         if w[4]:
             self._wgrad(dz, pr.p2, pre + "4.weight", R, Z, Pd, acc, dev)

@@ -18,7 +18,7 @@ grad) the plan is the launch sequence those two cases always had.
 import fnmatch
 
 LINEARS = ("mlp.fc2", "mlp.fc1", "attn.proj", "attn.qkv")    # in backward order
-# the stage of a block's backward that completes a gradient (Engine._backward runs stages 1 .. stage[i] of block i):
+# the stage of a block's backward that completes a gradient (Engine._backward_block runs stages 1 .. stage[i] of block i):
 #   1 dy2 -> fc2 | 2 da1 -> fc1 | 3 LN2 backward + gate: dy1 -> proj | 4 attention (+ qk-norm) backward: dqkv -> qkv, q/k norm
 #   5 LN1 backward and the block's modulation gradients (its adaLN rows; dx for the block below)
 STAGE_OF = {"mlp.fc2": 1, "mlp.fc1": 2, "attn.proj": 3, "attn.qkv": 4}

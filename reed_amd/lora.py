@@ -9,7 +9,7 @@ of an adapted weight becomes r(W') (arena.ParamArena.merge_lora -> csrc/lora.hip
 the transposed and MX-fp8 copies follow by their own mechanism.  The forward, the input gradients, the samplers, fp8 sampling and
 the EMA copy therefore run the kernels they always ran: inference costs nothing extra.  (A merged forward cannot carry LoRA
 dropout; none is offered.)  The backward takes the adapters' gradients from the (dy, x) pair of the linear
-(Engine._lora_grads -> reed_lora_grads), beside the base weight's gradient or — the usual case, the base frozen — instead of it.
+(Engine._lin_grads -> Engine._lora_grads -> reed_lora_grads), beside the base weight's gradient or — the usual case, the base frozen — instead of it.
 
 This module: the configuration check, the adapter file, the merged export, and
 
