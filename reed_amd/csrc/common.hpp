@@ -84,6 +84,21 @@ extern "C" void reed_set_error(const char* fmt, ...);
     }                                                              \
   } while (0)
 
+// A kernel that takes more than the default 64 KiB of dynamic LDS asks for it once: the first launch through `done` (a launcher's
+// function-local static, one per instantiation) sets the attribute on `kernel`, and on `kernel2` where two forms share the flag.
+// A refusal is reported and leaves `done` false.
+inline int reed_reserve_lds(bool& done, const void* kernel, int bytes, const char* who, const void* kernel2 = nullptr) {
+  if (done) return REED_OK;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess && kernel2) e = hipFuncSetAttribute(kernel2, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) {
+    reed_set_error("%s: cannot reserve %d bytes of LDS: %s", who, bytes, hipGetErrorString(e));
+    return (int)e;
+  }
+  done = true;
+  return REED_OK;
+}
+
 // ---- scalar helpers -------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }   // RNE, NaN-preserving (v_cvt_pk_bf16_f32)

@@ -1,5 +1,8 @@
 // Internal GEMM interface (see gemm.hip). Public C ABI is in include/reed_hip.h.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "common.hpp"
 
 enum { LAY_NT = 0, LAY_NN = 1, LAY_TN = 2,
@@ -38,13 +41,14 @@ enum {
 };
 constexpr int SWIGLU_GROUP = 8;   // = the 8 columns a lane of tile_epilogue owns: the partner sits in the neighbouring lane
 
-// Sets of epilogues as bit masks over the EPI_* values: every "which epilogues" question of the selection (gemm_plan.cpp) has
-// its one answer here.
+// Sets of epilogues as bit masks over the EPI_* values: every "which epilogues" question has its one answer here, for the
+// selection (gemm_plan.cpp) and for the launchers alike.
 template <class... E>
 constexpr unsigned epi_set(E... e) { return ((1u << e) | ...); }
 constexpr bool epi_in(unsigned set, int epi) { return epi >= 0 && epi < 32 && ((set >> epi) & 1u) != 0; }
-// -- per kernel and layout: has an instantiation / is allowed
-// the bf16-output epilogues, all built for the 256x144 tile
+// -- per kernel and layout: the epilogues the kernel is INSTANTIATED for.  Each launcher hands its set to epi_dispatch (below), so
+// a kernel exists for exactly the members; the selection reads the same constants, so it cannot plan a launch that is not built.
+// the bf16-output epilogues, all built for the 256x144 tile (NT and NN)
 constexpr unsigned EPIS_144 = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_QGELU, EPI_GELU_ERF,
                                       EPI_RES_BF16, EPI_GELU_G, EPI_SILU_G, EPI_MUL);
 // the 256x288 tile: the epilogues of the two 4608-wide GEMMs it was built for (fc1 forward, fc2 input gradient)
@@ -53,13 +57,17 @@ constexpr unsigned EPIS_288 = epi_set(EPI_BF16, EPI_GELU, EPI_GELU_G, EPI_DGELU,
 // SWIGLU (tower epilogues); - DGELU, DSILU, MUL: as found (a forward has none of them)
 constexpr unsigned EPIS_SKINNY = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_QGELU, EPI_GELU_ERF, EPI_GELU_G, EPI_SILU_G, EPI_RES_BF16,
                                          EPI_LS_RES, EPI_GATE_RES, EPI_SWIGLU);
-// the four-wave 256^2 kernel.  QuickGELU / exact-GELU are built for it and NOT eligible: they stay on the 8-wave kernel — their
-// VALU work (erff, two roundings per element) needs two waves per SIMD to hide its own latency; measured 0.93 vs 0.64 ms on the
-// ViT-L fc1 shape.  DSILU is missing from the NT set as found.
+// the four-wave 256^2 kernel.  QuickGELU / exact-GELU are not eligible and no longer built for it: they stay on the 8-wave
+// kernel — their VALU work (erff, two roundings per element) needs two waves per SIMD to hide its own latency; measured 0.93 vs
+// 0.64 ms on the ViT-L fc1 shape.  DSILU is missing from the NT set as found.
 constexpr unsigned EPIS_256W_NT = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_GELU_G, EPI_SILU_G, EPI_RES_BF16, EPI_LS_RES,
                                           EPI_BF16_DOT, EPI_DGELU, EPI_MUL, EPI_SWIGLU);
 // input gradients on the weights as they are: the backward's epilogues only
 constexpr unsigned EPIS_256W_NN = epi_set(EPI_BF16, EPI_BF16_DOT, EPI_DGELU, EPI_DSILU, EPI_MUL);
+constexpr unsigned epis_256w(int layout) { return layout == LAY_NT ? EPIS_256W_NT : EPIS_256W_NN; }
+// epilogue 13 is asked for as the plain store's kernel plus the dot (reed_gemm_plan_shape): wherever one is built, both are
+static_assert(epi_in(EPIS_256W_NT, EPI_BF16) == epi_in(EPIS_256W_NT, EPI_BF16_DOT) &&
+              epi_in(EPIS_256W_NN, EPI_BF16) == epi_in(EPIS_256W_NN, EPI_BF16_DOT), "four-wave 256^2: epilogues 0 and 13 go together");
 // the 256^2 kernels' re-dealt ragged last column tile (<= 128 live columns) counts ~0.6 of a tile in the cost model for these:
 // the bf16-output epilogues = EPIS_144, + LS_RES, SWIGLU as found
 constexpr unsigned EPIS_RAGGED_COL = EPIS_144 | epi_set(EPI_LS_RES, EPI_SWIGLU);
@@ -70,8 +78,26 @@ constexpr unsigned EPIS_NT_ONLY = epi_set(EPI_LS_RES, EPI_SWIGLU);
 constexpr bool epi_layout_ok(int layout, int epi, int N, int split_k) {
   return !epi_in(EPIS_NT_ONLY, epi) || (layout == LAY_NT && split_k <= 1 && (epi != EPI_SWIGLU || N % 128 == 0));
 }
-constexpr unsigned EPIS_128_NT = (1u << 18) - 1u - epi_set(EPI_BF16_DOT);
+constexpr int EPI_COUNT = 18;   // one past the largest EPI_* value
+constexpr unsigned EPIS_128_NT = (1u << EPI_COUNT) - 1u - epi_set(EPI_BF16_DOT);
 constexpr unsigned EPIS_256X8_TN = epi_set(EPI_F32, EPI_ADDF32_RB, EPI_ATOMIC_F32);
+constexpr unsigned epis_128(int layout) { return layout == LAY_NT ? EPIS_128_NT : EPIS_128_NT & ~EPIS_NT_ONLY; }
+constexpr unsigned epis_256x8(int layout) { return layout == LAY_TN ? EPIS_256X8_TN : epis_128(layout); }
+// the MX-fp8 block GEMM (gemm_mxfp8.hip): the three epilogues of the inference forward's block linears
+constexpr unsigned EPIS_MXFP8 = epi_set(EPI_BF16, EPI_GELU, EPI_GATE_RES);
+// the fp32-operand build's one kernel (gemm_f32.hip; its epilogue is a run-time switch): every layout.  GELU_ERF arrives as QGELU
+// with GemmArgs::act_variant = 1, SWIGLU is not part of that build
+constexpr unsigned EPIS_F32 = epi_set(EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB,
+                                      EPI_ATOMIC_F32, EPI_QGELU, EPI_RES_BF16, EPI_LS_RES, EPI_GELU_G, EPI_SILU_G, EPI_MUL);
+// the 128^2 kernel is where the selection ends when nothing else applies: what any other kernel builds on a layout, it builds too
+// (13 aside: a shape whose plain store lands there is answered with REED_ERR_UNSUPPORTED), and so does the fp32-operand build
+static_assert(((EPIS_144 | EPIS_288 | EPIS_SKINNY | EPIS_256W_NT) & ~(EPIS_128_NT | epi_set(EPI_BF16_DOT))) == 0 &&
+                  ((EPIS_144 | EPIS_256W_NN) & ~(epis_128(LAY_NN) | epi_set(EPI_BF16_DOT))) == 0 &&
+                  (EPIS_256X8_TN & ~epis_128(LAY_TN)) == 0 && (EPIS_F32 & ~EPIS_128_NT) == 0,
+              "a kernel builds an epilogue that the 128^2 kernel lacks on that layout");
+// the sets the cost model and the splits read describe epilogues that exist
+static_assert(((EPIS_RAGGED_COL | EPIS_NT_ONLY) & ~EPIS_128_NT) == 0, "the cost model names an epilogue that no kernel builds");
+
 // -- semantic
 // the row index carries no meaning (rows may go out as two launches): EPIS_RAGGED_COL - GATE_RES (the gate is per sample =
 // per block of rows); the head-dot slots of epilogue 13 and the fp32 outputs are left alone
@@ -83,6 +109,27 @@ constexpr unsigned EPIS_COLS_FREE = EPIS_144;
 // bytes per element of C and of R: the two fp32-residual epilogues have fp32 outputs; the splits take bf16 for everything else
 // in their sets
 constexpr int epi_out_bytes(int epi) { return epi == EPI_GATE_RES || epi == EPI_LS_RES ? 4 : 2; }
+
+// Launch-side reading of a set: calls f(std::integral_constant<int, E>{}) for the one member E of SET equal to `epi` and returns
+// true; for any other value calls nothing and returns false.  f's body is instantiated for the members only, so a launcher that
+// dispatches over its set builds a kernel for exactly that set.  (A chain of at most EPI_COUNT compares on the host.)
+template <unsigned SET, int E, class F>
+bool epi_dispatch_one(int epi, F& f) {
+  if constexpr (epi_in(SET, E)) {
+    if (epi == E) {
+      f(std::integral_constant<int, E>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <unsigned SET, class F, int... E>
+bool epi_dispatch_seq(int epi, F& f, std::integer_sequence<int, E...>) { return (epi_dispatch_one<SET, E>(epi, f) || ...); }
+template <unsigned SET, class F>
+bool epi_dispatch(int epi, F&& f) {
+  static_assert((SET >> EPI_COUNT) == 0, "epi_dispatch: the set has a member that is no epilogue");
+  return epi_dispatch_seq<SET>(epi, f, std::make_integer_sequence<int, EPI_COUNT>{});
+}
 
 struct GemmArgs {
   const bf16* P;

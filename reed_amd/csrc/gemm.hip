@@ -186,12 +186,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs a) {
 
 template <int LAY, int EPI>
 int launch(const GemmArgs& a, int splits, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_kernel<LAY, EPI>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_kernel<LAY, EPI>, 2 * STAGE_BYTES, "gemm")) return rc;
   const int ntm = cdiv(a.M, BM), ntn = a.N / BN;
   dim3 grid(ntm * ntn, splits, 1);
   REED_KLAUNCH((gemm_kernel<LAY, EPI>), grid, dim3(256), 2 * STAGE_BYTES, stream, a);
@@ -201,29 +197,8 @@ int launch(const GemmArgs& a, int splits, hipStream_t stream) {
 
 template <int LAY>
 int dispatch_epi(int epi, const GemmArgs& a, int splits, hipStream_t s) {
-  switch (epi) {
-    case EPI_BF16: return launch<LAY, EPI_BF16>(a, splits, s);
-    case EPI_GELU: return launch<LAY, EPI_GELU>(a, splits, s);
-    case EPI_SILU: return launch<LAY, EPI_SILU>(a, splits, s);
-    case EPI_GATE_RES: return launch<LAY, EPI_GATE_RES>(a, splits, s);
-    case EPI_DGELU: return launch<LAY, EPI_DGELU>(a, splits, s);
-    case EPI_DSILU: return launch<LAY, EPI_DSILU>(a, splits, s);
-    case EPI_GELU_G: return launch<LAY, EPI_GELU_G>(a, splits, s);
-    case EPI_SILU_G: return launch<LAY, EPI_SILU_G>(a, splits, s);
-    case EPI_MUL: return launch<LAY, EPI_MUL>(a, splits, s);
-    case EPI_F32: return launch<LAY, EPI_F32>(a, splits, s);
-    case EPI_ADDF32_RB: return launch<LAY, EPI_ADDF32_RB>(a, splits, s);
-    case EPI_ATOMIC_F32: return launch<LAY, EPI_ATOMIC_F32>(a, splits, s);
-    case EPI_QGELU: return launch<LAY, EPI_QGELU>(a, splits, s);
-    case EPI_GELU_ERF: return launch<LAY, EPI_GELU_ERF>(a, splits, s);
-    case EPI_RES_BF16: return launch<LAY, EPI_RES_BF16>(a, splits, s);
-    case EPI_LS_RES:
-      if constexpr (LAY == LAY_NT) return launch<LAY, EPI_LS_RES>(a, splits, s);
-      break;
-    case EPI_SWIGLU:
-      if constexpr (LAY == LAY_NT) return launch<LAY, EPI_SWIGLU>(a, splits, s);
-      break;
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<epis_128(LAY)>(epi, [&](auto e) { rc = launch<LAY, decltype(e)::value>(a, splits, s); })) return rc;
   reed_set_error("reed_gemm: unknown epilogue %d", epi);
   return REED_ERR_ARG;
 }

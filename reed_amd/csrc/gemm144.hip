@@ -347,19 +347,13 @@ static bool use_loader_waves() { return true; }   // (the 8-wave form without th
 
 template <int LAY, int EPI>
 int launch144(const GemmArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
+  static bool reserved = false;
   constexpr bool HAS_LW = EPI == EPI_BF16 || EPI == EPI_GATE_RES || EPI == EPI_GELU || EPI == EPI_DGELU || EPI == EPI_GELU_G ||
                           EPI == EPI_MUL;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm144_kernel<LAY, EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       LDS4);
-    if constexpr (HAS_LW) {
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gemm144_kernel<LAY, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS4);
-    }
-    if (e != hipSuccess) { reed_set_error("gemm144: cannot reserve 150 KiB LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  const void* with_loader_waves = nullptr;
+  if constexpr (HAS_LW) with_loader_waves = (const void*)gemm144_kernel<LAY, EPI, true>;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm144_kernel<LAY, EPI, false>, LDS4, "gemm144", with_loader_waves))
+    return rc;
   dim3 grid(cdiv(a.M, BM4) * (a.N / BN4), 1, 1);
   if constexpr (HAS_LW) {
     if (use_loader_waves()) {
@@ -375,20 +369,8 @@ int launch144(const GemmArgs& a, hipStream_t stream) {
 
 template <int LAY>
 int dispatch144(int epi, const GemmArgs& a, hipStream_t s) {
-  switch (epi) {
-    case EPI_BF16: return launch144<LAY, EPI_BF16>(a, s);
-    case EPI_GELU: return launch144<LAY, EPI_GELU>(a, s);
-    case EPI_SILU: return launch144<LAY, EPI_SILU>(a, s);
-    case EPI_GATE_RES: return launch144<LAY, EPI_GATE_RES>(a, s);
-    case EPI_DGELU: return launch144<LAY, EPI_DGELU>(a, s);
-    case EPI_DSILU: return launch144<LAY, EPI_DSILU>(a, s);
-    case EPI_GELU_G: return launch144<LAY, EPI_GELU_G>(a, s);
-    case EPI_SILU_G: return launch144<LAY, EPI_SILU_G>(a, s);
-    case EPI_MUL: return launch144<LAY, EPI_MUL>(a, s);
-    case EPI_QGELU: return launch144<LAY, EPI_QGELU>(a, s);
-    case EPI_GELU_ERF: return launch144<LAY, EPI_GELU_ERF>(a, s);
-    case EPI_RES_BF16: return launch144<LAY, EPI_RES_BF16>(a, s);
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<EPIS_144>(epi, [&](auto e) { rc = launch144<LAY, decltype(e)::value>(a, s); })) return rc;
   reed_set_error("reed_gemm(256x144): epilogue %d has no bf16-output form", epi);
   return REED_ERR_ARG;
 }

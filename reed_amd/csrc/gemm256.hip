@@ -329,52 +329,19 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmArgs a) {
 
 template <int LAY, int EPI>
 int launch256(const GemmArgs& a, int splits, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm256_kernel<LAY, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) { reed_set_error("gemm256: cannot reserve 128 KiB LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm256_kernel<LAY, EPI>, LDS_BYTES, "gemm256")) return rc;
   dim3 grid(cdiv(a.M, BM2) * cdiv(a.N, BN2), splits, 1);
   REED_KLAUNCH((gemm256_kernel<LAY, EPI>), grid, dim3(512), LDS_BYTES, stream, a);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }
 
+// (on TN — weight gradients — the fp32 outputs only: the bf16-output epilogues are never launched there)
 template <int LAY>
 int dispatch256(int epi, const GemmArgs& a, int splits, hipStream_t s) {
-  if constexpr (LAY == LAY_TN) {   // weight gradients: fp32 outputs only (the bf16-output epilogues are never launched on TN)
-    switch (epi) {
-      case EPI_F32: return launch256<LAY, EPI_F32>(a, splits, s);
-      case EPI_ADDF32_RB: return launch256<LAY, EPI_ADDF32_RB>(a, splits, s);
-      case EPI_ATOMIC_F32: return launch256<LAY, EPI_ATOMIC_F32>(a, splits, s);
-    }
-  } else {
-    switch (epi) {
-      case EPI_BF16: return launch256<LAY, EPI_BF16>(a, splits, s);
-      case EPI_GELU: return launch256<LAY, EPI_GELU>(a, splits, s);
-      case EPI_SILU: return launch256<LAY, EPI_SILU>(a, splits, s);
-      case EPI_GATE_RES: return launch256<LAY, EPI_GATE_RES>(a, splits, s);
-      case EPI_DGELU: return launch256<LAY, EPI_DGELU>(a, splits, s);
-      case EPI_DSILU: return launch256<LAY, EPI_DSILU>(a, splits, s);
-      case EPI_GELU_G: return launch256<LAY, EPI_GELU_G>(a, splits, s);
-      case EPI_SILU_G: return launch256<LAY, EPI_SILU_G>(a, splits, s);
-      case EPI_MUL: return launch256<LAY, EPI_MUL>(a, splits, s);
-      case EPI_F32: return launch256<LAY, EPI_F32>(a, splits, s);
-      case EPI_ADDF32_RB: return launch256<LAY, EPI_ADDF32_RB>(a, splits, s);
-      case EPI_ATOMIC_F32: return launch256<LAY, EPI_ATOMIC_F32>(a, splits, s);
-      case EPI_QGELU: return launch256<LAY, EPI_QGELU>(a, splits, s);
-      case EPI_GELU_ERF: return launch256<LAY, EPI_GELU_ERF>(a, splits, s);
-      case EPI_RES_BF16: return launch256<LAY, EPI_RES_BF16>(a, splits, s);
-      case EPI_LS_RES:
-        if constexpr (LAY == LAY_NT) return launch256<LAY, EPI_LS_RES>(a, splits, s);
-        break;
-      case EPI_SWIGLU:
-        if constexpr (LAY == LAY_NT) return launch256<LAY, EPI_SWIGLU>(a, splits, s);
-        break;
-    }
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<epis_256x8(LAY)>(epi, [&](auto e) { rc = launch256<LAY, decltype(e)::value>(a, splits, s); })) return rc;
   reed_set_error("reed_gemm(256^2): epilogue %d is not built for layout %d", epi, LAY);
   return REED_ERR_ARG;
 }

@@ -957,55 +957,29 @@ __global__ __launch_bounds__(256, 1) void gemm256w_tn_group_kernel(TnGroupW g) {
 // the tile rows per XCD-local group (GemmArgs::tile_gm) are gemm_plan.cpp's decision.
 template <int LAY, int EPI>
 int launch256w(const GemmArgs& a, bool persistent, int grid, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm256wp_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm256w_kernel<LAY, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_W);
-    if (e != hipSuccess) { reed_set_error("gemm256w: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm256wp_kernel<LAY, EPI>, LDS_W, "gemm256w",
+                                      (const void*)gemm256w_kernel<LAY, EPI>))
+    return rc;
   if (persistent) REED_KLAUNCH((gemm256wp_kernel<LAY, EPI>), dim3(grid), dim3(256), LDS_W, stream, a);
   else REED_KLAUNCH((gemm256w_kernel<LAY, EPI>), dim3(grid), dim3(256), LDS_W, stream, a);
   REED_LAUNCH_CHECK();
   return REED_OK;
 }
 
+// NT: the forward GEMMs (SiT blocks, the projector MLP, the frozen towers) and the input gradients as NT GEMMs on a transposed copy
+// of the weights (engine.py: both operands k-contiguous); NN: the input gradients on the weights as they are (k-strided B operand)
 template <int LAY>
 int dispatch256w(int epi, const GemmArgs& a, bool persistent, int grid, hipStream_t s) {
-  if constexpr (LAY == LAY_NT) {   // forward GEMMs: SiT blocks, the projector MLP, the frozen towers
-    switch (epi) {
-      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, persistent, grid, s);
-      case EPI_GELU: return launch256w<LAY, EPI_GELU>(a, persistent, grid, s);
-      case EPI_SILU: return launch256w<LAY, EPI_SILU>(a, persistent, grid, s);
-      case EPI_GELU_G: return launch256w<LAY, EPI_GELU_G>(a, persistent, grid, s);
-      case EPI_SILU_G: return launch256w<LAY, EPI_SILU_G>(a, persistent, grid, s);
-      case EPI_GATE_RES: return launch256w<LAY, EPI_GATE_RES>(a, persistent, grid, s);
-      case EPI_RES_BF16: return launch256w<LAY, EPI_RES_BF16>(a, persistent, grid, s);
-      case EPI_LS_RES: return launch256w<LAY, EPI_LS_RES>(a, persistent, grid, s);
-      case EPI_QGELU: return launch256w<LAY, EPI_QGELU>(a, persistent, grid, s);
-      case EPI_GELU_ERF: return launch256w<LAY, EPI_GELU_ERF>(a, persistent, grid, s);
-      case EPI_SWIGLU: return launch256w<LAY, EPI_SWIGLU>(a, persistent, grid, s);
-      // round 6: the input gradients as NT GEMMs on a transposed copy of the weights (engine.py: both operands k-contiguous)
-      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, persistent, grid, s);
-      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, persistent, grid, s);
-      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, persistent, grid, s);
-    }
-  } else {                         // input gradients (on the weights as they are: k-strided B operand)
-    switch (epi) {
-      case EPI_BF16: return launch256w<LAY, EPI_BF16>(a, persistent, grid, s);
-      case EPI_BF16_DOT: return launch256w<LAY, EPI_BF16_DOT>(a, persistent, grid, s);
-      case EPI_DGELU: return launch256w<LAY, EPI_DGELU>(a, persistent, grid, s);
-      case EPI_DSILU: return launch256w<LAY, EPI_DSILU>(a, persistent, grid, s);
-      case EPI_MUL: return launch256w<LAY, EPI_MUL>(a, persistent, grid, s);
-    }
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<epis_256w(LAY)>(epi, [&](auto e) { rc = launch256w<LAY, decltype(e)::value>(a, persistent, grid, s); })) return rc;
   reed_set_error("reed_gemm(256w): epilogue %d not built for this layout", epi);
   return REED_ERR_UNSUPPORTED;
 }
 
 }  // namespace
 
-// (eligible shapes and epilogues — EPIS_256W_NT / EPIS_256W_NN, fewer than are built above —: gemm_plan.cpp, gemm.h)
+// (eligible shapes: gemm_plan.cpp; the epilogues built = eligible, EPIS_256W_NT / EPIS_256W_NN: gemm.h)
 int reed_gemm256w_launch(int layout, int epi, GemmArgs a, bool persistent, int grid, hipStream_t stream) {
   if (layout == LAY_NT) return dispatch256w<LAY_NT>(epi, a, persistent, grid, stream);
   return dispatch256w<LAY_NN>(epi, a, persistent, grid, stream);
@@ -1103,13 +1077,10 @@ int reed_gemm256w_tn_group_launch(int n, const GemmArgs* probs, hipStream_t stre
   if (w4_deal(n, M, N, db, ncu, g.item) == 0) return REED_OK;
   g.n = n;
   g.wpx = ncu / 8;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm256w_tn_group_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm256w_tn_group_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TN);
-    if (e != hipSuccess) { reed_set_error("gemm256w: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm256w_tn_group_kernel<0>, LDS_TN, "gemm256w (grouped TN)",
+                                      (const void*)gemm256w_tn_group_kernel<1>))
+    return rc;
   bool accum = false;
   for (int i = 0; i < n; ++i) accum = accum || probs[i].accumulate != 0;
   if (accum) REED_KLAUNCH(gemm256w_tn_group_kernel<1>, dim3(ncu), dim3(256), LDS_TN, stream, g);

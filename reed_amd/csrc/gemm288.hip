@@ -218,12 +218,8 @@ __global__ __launch_bounds__(512) void gemm288_kernel(GemmArgs a) {
 
 template <int EPI>
 int launch288(const GemmArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm288_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-    if (e != hipSuccess) { reed_set_error("gemm288: cannot reserve 136 KiB LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm288_kernel<EPI>, LDS8, "gemm288")) return rc;
   dim3 grid(cdiv(a.M, BM8) * (a.N / BN8), 1, 1);
   REED_KLAUNCH((gemm288_kernel<EPI>), grid, dim3(512), LDS8, stream, a);
   REED_LAUNCH_CHECK();
@@ -242,13 +238,8 @@ int launch288(const GemmArgs& a, hipStream_t stream) {
 // rows only two 68 KiB stages fit the 160 KiB (the first form: the same 50 us per round).  So the heuristic does NOT take it
 // (REED_GEMM288=1 does); force_tile 288 runs it on any shape it accepts (tests, tools/r6/t288.py).
 int reed_gemm288_launch(int epi, GemmArgs a, hipStream_t stream) {
-  switch (epi) {
-    case EPI_BF16: return launch288<EPI_BF16>(a, stream);
-    case EPI_GELU: return launch288<EPI_GELU>(a, stream);
-    case EPI_GELU_G: return launch288<EPI_GELU_G>(a, stream);
-    case EPI_DGELU: return launch288<EPI_DGELU>(a, stream);
-    case EPI_MUL: return launch288<EPI_MUL>(a, stream);
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<EPIS_288>(epi, [&](auto e) { rc = launch288<decltype(e)::value>(a, stream); })) return rc;
   reed_set_error("reed_gemm(256x288): epilogue %d has no instantiation", epi);
   return REED_ERR_ARG;
 }

@@ -508,12 +508,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_split_kernel(GemmArgs a, int 
 template <int LAY, int W>
 int launch_w(const GemmArgs& a, int epi, int splits, hipStream_t stream, ConvGeo cg) {
   constexpr int lds = 2 * 2 * Geo<W>::TILE_FLOATS * (int)sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_f32_kernel<LAY, W>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) { reed_set_error("gemm_f32: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_f32_kernel<LAY, W>, lds, "gemm_f32")) return rc;
   dim3 grid(cdiv(a.M, Geo<W>::BT) * cdiv(a.N, Geo<W>::BT), splits, 1);
   REED_KLAUNCH((gemm_f32_kernel<LAY, W>), grid, dim3(Geo<W>::NT), lds, stream, a, epi, cg);
   REED_LAUNCH_CHECK();
@@ -522,12 +518,8 @@ int launch_w(const GemmArgs& a, int epi, int splits, hipStream_t stream, ConvGeo
 
 template <int LAY>
 int launch_split(const GemmArgs& a, int epi, int splits, hipStream_t stream, ConvGeo cg) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_f32_split_kernel<LAY>, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_LDS);
-    if (e != hipSuccess) { reed_set_error("gemm_f32 (split): cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_f32_split_kernel<LAY>, SPLIT_LDS, "gemm_f32 (split)")) return rc;
   dim3 grid(cdiv(a.M, 128) * cdiv(a.N, 128), splits, 1);
   REED_KLAUNCH((gemm_f32_split_kernel<LAY>), grid, dim3(256), SPLIT_LDS, stream, a, epi, cg);
   REED_LAUNCH_CHECK();
@@ -604,12 +596,7 @@ static int plan_f32(int& layout, int epi, int M, int N, int K, int& splits, bool
   if (layout == LAY_TN_TALL || layout == LAY_TN_WIDE) layout = LAY_TN;   // tile hints of the 16-bit weight-gradient kernel
   if (layout == LAY_TN) REED_CHECK_ARG(M % 4 == 0, "reed_gemm(TN, fp32): M=%d must be a multiple of 4", M);
   else REED_CHECK_ARG(K % 4 == 0, "reed_gemm(NT/NN, fp32): K=%d must be a multiple of 4", K);
-  switch (epi) {
-    case EPI_BF16: case EPI_GELU: case EPI_SILU: case EPI_GATE_RES: case EPI_DGELU: case EPI_DSILU: case EPI_F32:
-    case EPI_ADDF32_RB: case EPI_ATOMIC_F32: case EPI_QGELU: case EPI_RES_BF16: case EPI_LS_RES:
-    case EPI_GELU_G: case EPI_SILU_G: case EPI_MUL: break;
-    default: reed_set_error("reed_gemm: unknown epilogue %d", epi); return REED_ERR_ARG;
-  }
+  REED_CHECK_ARG(epi_in(EPIS_F32, epi), "reed_gemm: unknown epilogue %d", epi);
   if (splits < 1) splits = 1;
   const int ksteps = cdiv(K, 64);
   const int per = cdiv(ksteps, splits);

@@ -215,11 +215,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmArgs a, MxOperan
 
 template <int EPI>
 int launch(const GemmArgs& a, const MxOperands& mx, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_mxfp8_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_mxfp8_kernel<EPI>, 2 * STAGE_BYTES, "gemm_mxfp8")) return rc;
   const int ntm = cdiv(a.M, BM), ntn = a.N / BN;
   REED_KLAUNCH((gemm_mxfp8_kernel<EPI>), dim3(ntm * ntn), dim3(256), 2 * STAGE_BYTES, stream, a, mx);
   REED_LAUNCH_CHECK();
@@ -278,10 +275,7 @@ extern "C" int reed_gemm_mxfp8(int epilogue, const void* Aq, int64_t lda, const 
   a.rows_per_gate = rows_per_gate > 0 ? rows_per_gate : 1;
   const MxOperands mx{(const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws,
                       (long)lda, (long)ldas, (long)ldw, (long)ldws};
-  switch (epilogue) {
-    case EPI_BF16: return launch<EPI_BF16>(a, mx, (hipStream_t)stream);
-    case EPI_GELU: return launch<EPI_GELU>(a, mx, (hipStream_t)stream);
-    case EPI_GATE_RES: return launch<EPI_GATE_RES>(a, mx, (hipStream_t)stream);
-  }
-  return REED_ERR_ARG;
+  int rc = REED_ERR_ARG;   // (reed_gemm_mxfp8_plan has refused every epilogue outside the set)
+  epi_dispatch<EPIS_MXFP8>(epilogue, [&](auto e) { rc = launch<decltype(e)::value>(a, mx, (hipStream_t)stream); });
+  return rc;
 }

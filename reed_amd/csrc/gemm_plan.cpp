@@ -84,7 +84,7 @@ bool eligible288(const GemmShape& s) {
 // four-wave 256^2
 bool eligible256w(const GemmShape& s) {
   return nt_or_nn(s.layout) && s.splits <= 1 && s.K % 64 == 0 && s.K >= 128 && s.N % 128 == 0 &&
-         epi_in(s.layout == LAY_NT ? EPIS_256W_NT : EPIS_256W_NN, s.epi);
+         epi_in(epis_256w(s.layout), s.epi);
 }
 // skinny: NT, K a multiple of 64, N of 64, no split-K
 bool eligible_skinny(const GemmShape& s) {
@@ -223,8 +223,7 @@ int square_built(const GemmShape& s, bool eight_wave) {
     reed_set_error("reed_gemm: unknown layout %d", s.layout);
     return REED_ERR_ARG;
   }
-  const unsigned built = s.layout == LAY_NT ? EPIS_128_NT : eight_wave && s.layout == LAY_TN ? EPIS_256X8_TN : EPIS_128_NT & ~EPIS_NT_ONLY;
-  if (epi_in(built, s.epi)) return REED_OK;
+  if (epi_in(eight_wave ? epis_256x8(s.layout) : epis_128(s.layout), s.epi)) return REED_OK;
   if (eight_wave) reed_set_error("reed_gemm(256^2): epilogue %d is not built for layout %d", s.epi, s.layout);
   else reed_set_error("reed_gemm: unknown epilogue %d", s.epi);
   return REED_ERR_ARG;
@@ -422,7 +421,7 @@ extern "C" int reed_gemm_mxfp8_plan(int epilogue, int M, int N, int K) {
   (void)M; (void)N; (void)K;
   REED_CHECK_ARG(false, "reed_gemm_mxfp8: epilogue %d: not part of the fp32-operand build (use the bf16 / fp16 library)", epilogue);
 #else
-  REED_CHECK_ARG(epi_in(epi_set(EPI_BF16, EPI_GELU, EPI_GATE_RES), epilogue), "reed_gemm_mxfp8: epilogue %d: 0, 1 or 3", epilogue);
+  REED_CHECK_ARG(epi_in(EPIS_MXFP8, epilogue), "reed_gemm_mxfp8: epilogue %d: 0, 1 or 3", epilogue);
   REED_CHECK_ARG(M >= 1 && N >= 128 && N % 128 == 0 && K >= 128 && K % 128 == 0,
                  "reed_gemm_mxfp8: M=%d >= 1, N=%d and K=%d positive multiples of 128", M, N, K);
 #endif

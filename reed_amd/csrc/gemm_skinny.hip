@@ -104,12 +104,8 @@ __global__ __launch_bounds__(64) void gemm_skinny_kernel(GemmArgs a) {
 
 template <int EPI>
 int launch_skinny(const GemmArgs& a, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_skinny_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, SLDS);
-    if (e != hipSuccess) { reed_set_error("gemm_skinny: cannot reserve LDS: %s", hipGetErrorString(e)); return (int)e; }
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_skinny_kernel<EPI>, SLDS, "gemm_skinny")) return rc;
   const int nwg = cdiv(a.M, 16) * (a.N / 64);
   REED_KLAUNCH((gemm_skinny_kernel<EPI>), dim3(nwg), dim3(64), SLDS, stream, a);
   REED_LAUNCH_CHECK();
@@ -120,19 +116,8 @@ int launch_skinny(const GemmArgs& a, hipStream_t stream) {
 
 // (shapes: NT, an epilogue of EPIS_SKINNY, K a multiple of 64, N of 64, no split-K: gemm_plan.cpp)
 int reed_gemm_skinny_launch(int epi, GemmArgs a, hipStream_t stream) {
-  switch (epi) {
-    case EPI_BF16: return launch_skinny<EPI_BF16>(a, stream);
-    case EPI_GELU: return launch_skinny<EPI_GELU>(a, stream);
-    case EPI_SILU: return launch_skinny<EPI_SILU>(a, stream);
-    case EPI_GELU_G: return launch_skinny<EPI_GELU_G>(a, stream);
-    case EPI_SILU_G: return launch_skinny<EPI_SILU_G>(a, stream);
-    case EPI_QGELU: return launch_skinny<EPI_QGELU>(a, stream);
-    case EPI_GELU_ERF: return launch_skinny<EPI_GELU_ERF>(a, stream);
-    case EPI_RES_BF16: return launch_skinny<EPI_RES_BF16>(a, stream);
-    case EPI_LS_RES: return launch_skinny<EPI_LS_RES>(a, stream);
-    case EPI_GATE_RES: return launch_skinny<EPI_GATE_RES>(a, stream);
-    case EPI_SWIGLU: return launch_skinny<EPI_SWIGLU>(a, stream);
-  }
+  int rc = REED_ERR_ARG;
+  if (epi_dispatch<EPIS_SKINNY>(epi, [&](auto e) { rc = launch_skinny<decltype(e)::value>(a, stream); })) return rc;
   reed_set_error("gemm_skinny: epilogue %d not built", epi);
   return REED_ERR_UNSUPPORTED;
 }

@@ -275,11 +275,8 @@ template <bool WIDE>
 int launch_tn(const GemmArgs& a, int splits, hipStream_t stream) {
   constexpr int BMT = WIDE ? 128 : 256, BNT = WIDE ? 256 : 128;
   constexpr int LDS = 2 * 3 * SUB_BYTES;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_tn_kernel<WIDE>, LDS, "gemm_tn")) return rc;
   dim3 grid(cdiv(a.M, BMT) * (a.N / BNT), splits, 1);
   REED_KLAUNCH((gemm_tn_kernel<WIDE>), grid, dim3(256), LDS, stream, a);
   REED_LAUNCH_CHECK();
@@ -324,11 +321,8 @@ int reed_gemm_tn_group_launch(int n, const GemmArgs* probs, hipStream_t stream) 
   }
   if (g.compact) at = 8 * cdiv(at, 8);
   constexpr int LDS = 2 * 3 * SUB_BYTES;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
+  static bool reserved = false;
+  if (const int rc = reed_reserve_lds(reserved, (const void*)gemm_tn_group_kernel, LDS, "gemm_tn (grouped)")) return rc;
   REED_KLAUNCH(gemm_tn_group_kernel, dim3(at), dim3(256), LDS, stream, g);
   REED_LAUNCH_CHECK();
   return REED_OK;
