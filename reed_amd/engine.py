@@ -14,6 +14,8 @@ Each decision has one site: a block linear's forward launch (16-bit or MX-fp8) i
 gradients (grouped launch / own launch / adapters, as freeze.py's plan says) are Engine._lin_grads.  The backward runs as phases
 over one per-call record: _backward_final, _backward_block for each block from the top, _backward_tail (adaLN + conditioning),
 _backward_end (the buckets not yet fired, the inputs' gradients, the side stream's join) — full and truncated alike.
+With SiT.recompute set (recompute.py) the lowest blocks keep a checkpoint (x, y2) in place of their record and _backward_block
+starts by rebuilding it (_recompute_block: the forward's launches up to fc1); everything behind that reads the record as ever.
 """
 import contextlib
 import logging
@@ -24,6 +26,7 @@ import torch
 
 from . import ops
 from .freeze import LINEARS, FreezePlan
+from .recompute import max_tokens, recomputed_blocks, saved_activation_bytes
 from .ops import (NT, NN, TN, EPI_BF16, EPI_GELU, EPI_SILU, EPI_GATE_RES, EPI_DGELU, EPI_DSILU, EPI_F32, EPI_ADDF32_RB,
                   EPI_GELU_G, EPI_SILU_G, EPI_MUL)
 
@@ -111,6 +114,7 @@ class Engine:
         self.fused_delta = True
         self._fp8_logged = False  # the list of fp8 / 16-bit layers has been logged
         self._err = None         # sticky device flag: a label outside the embedding table was seen (see check_errors)
+        self.recomputed = 0      # blocks the last backward rebuilt from their checkpoints (SiT.recompute; recompute.py)
 
     def _check_dims(self, prec):
         """Shape restrictions of the build that evaluates the model: the 16-bit MFMA tiles want every GEMM width in multiples
@@ -174,6 +178,29 @@ class Engine:
                   "mlp.fc2": (EPI_GATE_RES, D, Hm)}
         return {n: ops.gemm_mxfp8_plan(e, M, N, K, precision=prec) for n, (e, N, K) in shapes.items()}
 
+    def max_tokens(self, precision=None):
+        """The largest B T of a forward whose backward writes parameter gradients (recompute.max_tokens: the 32-bit byte offsets
+        of the 16-bit weight-gradient GEMMs over their token-major operands, the widest being qkv's, the MLP's or a projector's)."""
+        widest = max(3 * self.D, self.Hm, self.m.projector_dim if self.m.z_dims else 0)
+        return max_tokens(widest, ops.half_dtype(precision or self.m.precision).itemsize, self.T, self.L.ada_rows)
+
+    def saved_activation_bytes(self, B, recompute=None, plan=None, inference=False):
+        """Bytes the tape of a training forward at batch B holds from the forward to the backward: the closed form of
+        recompute.saved_activation_bytes for this model.  recompute: a SiT.recompute value (None: the model's); plan: the
+        FreezePlan (None: that of the parameters' current requires_grad flags, no input gradient); inference: the forward's flag
+        (True: no projector runs)."""
+        m = self.m
+        pl = plan if plan is not None else self.plan_for()
+        rc = recomputed_blocks(m.recompute if recompute is None else recompute, pl.save)
+        projs = [] if inference else [(B * self.T if m.z_types[j] == "i" else B, m.projector_dim)
+                                      for j in range(len(self.tap_depth)) if pl.proj[j]["run"]]
+        return saved_activation_bytes(B, self.T, self.D, self.Hm, self.H, self.depth, ops.half_dtype(m.precision).itemsize, pl.save,
+                                      rc, self.C, m.input_size, self.L.ada_rows, bool(m.qk_norm), projs)
+
+    def _linear_fwd(self, name, epi, act, M, N, K, C, C2=None, ldc2=0, **kw):
+        """The 16-bit forward launch of block linear `name`: the forward's, and the one a recomputed block's rebuild repeats."""
+        ops.gemm(NT, epi, act, self.W(name + ".weight"), M, N, K, C, K, K, N, C2=C2, ldc2=ldc2, bias=self.W(name + ".bias"), **kw)
+
     def forward(self, x, t, y, inference, need_grad, drop, plan=None):
         """plan: the FreezePlan of this forward's backward (need_grad only; None = every block saves, as with every parameter
         trainable)."""
@@ -194,6 +221,10 @@ class Engine:
             raise ValueError(f"input {tuple(x.shape)} does not match (N,{self.C},{m.input_size},{m.input_size})")
         M = B * T
         self._check_dims(prec)
+        if need_grad and (plan is None or plan.any) and M > self.max_tokens(prec):
+            raise ValueError(f"reed_amd.SiT: a training forward of {B} x {T} = {M} tokens is past the {self.max_tokens(prec)} tokens the "
+                             f"weight-gradient kernels' 32-bit offsets cover at this width (reed_amd/recompute.py:max_tokens); use a "
+                             f"smaller local batch with gradient accumulation")
         self._shadow = self.A.ensure_shadow(prec)
         hdt = ops.half_dtype(prec)
         hb = self._hb = hdt.itemsize    # bytes per element of the operand / activation arrays (2; 4 in the fp32-operand build)
@@ -211,6 +242,7 @@ class Engine:
         tp = types.SimpleNamespace(B=B, blocks=[], proj={}, x=x, t=t, prec=prec, act_grad=sag, plan=plan) if need_grad else None
         # a partly frozen model (freeze.py): blocks below the lowest one whose backward runs save nothing
         save = plan.save if (need_grad and plan is not None) else [need_grad] * self.depth
+        rc = recomputed_blocks(m.recompute, save) if need_grad else [False] * self.depth   # (recompute.py; a bad value raises here)
         # epilogues of a layer whose saved array feeds the backward (gemm.h): derivative-saving forms when there is a backward
         epi_silu = EPI_SILU_G if need_grad and sag else EPI_SILU
         epi_gelu = EPI_GELU_G if need_grad and sag else EPI_GELU
@@ -288,9 +320,15 @@ class Engine:
                 ops.gemm_mxfp8(epi, aq, asc, wq, wsc, M, N, K, C, N if C is not None else 0, C2=C2,
                                ldc2=ldc2 if C2 is not None else 0, bias=self.W(name + ".bias"), **kw)
             else:
-                ops.gemm(NT, epi, act, self.W(name + ".weight"), M, N, K, C, K, K, N, C2=C2, ldc2=ldc2,
-                         bias=self.W(name + ".bias"), **kw)
+                self._linear_fwd(name, epi, act, M, N, K, C, C2, ldc2, **kw)
 
+        # recompute (recompute.py): the lowest blocks with a backward keep their input and y2 and run like the blocks that save
+        # nothing, on shared h / qkv / o / u and one shared xmid; Engine._recompute_block rebuilds their record in the backward
+        rc_left = sum(rc)
+        if rc_left:
+            if all(save):
+                h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
+            rc_buf = (h, qkv, o, u, f32(M, D))
         xcur = tok
         zs_by_proj = {}
         for i in range(self.depth):
@@ -301,7 +339,13 @@ class Engine:
                 kh = 0
             if pend:
                 self.A.wait(f"block{i}")
-            if save[i]:
+            keep = save[i] and not rc[i]     # this block's forward saves its activations
+            if rc[i]:
+                h, qkv, o, u, xmid = rc_buf
+                h2, a1, y1, y2 = h, None, None, bf(M, D)
+                mean1 = rstd1 = mean2 = rstd2 = lse = None
+                xout = f32(M, D)
+            elif save[i]:
                 h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
                 h2, a1, y1, y2 = bf(M, D), bf(M, Hm), bf(M, D), bf(M, D)
                 mean1, rstd1, mean2, rstd2 = f32(M), f32(M), f32(M), f32(M)
@@ -317,23 +361,28 @@ class Engine:
             qkv_a, qstats = qkv, None
             if m.qk_norm:
                 qkv_a = bf(M, 3 * D)
-                qstats = f32(M, 2, H, 2) if save[i] else None
+                qstats = f32(M, 2, H, 2) if keep else None
                 ops.qk_norm_fwd(qkv, self.Wf(b + "attn.q_norm.weight"), self.Wf(b + "attn.q_norm.bias"),
                                 self.Wf(b + "attn.k_norm.weight"), self.Wf(b + "attn.k_norm.bias"), qkv_a, qstats, M, H, hd)
             ops.attention_fwd(qkv_a, o, lse, B, T, H, hd)
             linear("attn.proj", EPI_GATE_RES, o, D, D, xmid, C2=y1, ldc2=D, R=xcur, ldr=D, gate=mb + 2 * hb * D, ldgate=Nall,
                    rows_per_gate=T)
             ops.ln_modulate_fwd(xmid, mb + 3 * hb * D, mb + 4 * hb * D, Nall, h2, mean2, rstd2, M, D, T)
-            linear("mlp.fc1", epi_gelu if save[i] else EPI_GELU, h2, Hm, D, a1, C2=u, ldc2=Hm)
+            linear("mlp.fc1", epi_gelu if keep else EPI_GELU, h2, Hm, D, a1, C2=u, ldc2=Hm)
             linear("mlp.fc2", EPI_GATE_RES, u, D, Hm, xout, C2=y2, ldc2=D, R=xmid, ldr=D, gate=mb + 5 * hb * D, ldgate=Nall,
                    rows_per_gate=T)
             if need_grad and not save[i]:
                 tp.blocks.append(None)
+            elif rc[i]:
+                tp.blocks.append(types.SimpleNamespace(rc=True, x=xcur, y2=y2))
+                rc_left -= 1
+                if not rc_left:   # the shared buffers go back before the blocks that save allocate theirs
+                    rc_buf = h = qkv = o = u = h2 = xmid = qkv_a = None
             elif need_grad:
                 tp.blocks.append(types.SimpleNamespace(x=xcur, mean1=mean1, rstd1=rstd1, h=h, qkv=qkv, qkv_a=qkv_a,
                                                        qstats=qstats, o=o, lse=lse,
                                                        y1=y1, xmid=xmid, mean2=mean2, rstd2=rstd2, h2=h2, a1=a1, u=u,
-                                                       y2=y2))
+                                                       y2=y2, rc=False))
             xcur = xout
             if not inference:
                 for j, dj in enumerate(self.tap_depth):
@@ -536,6 +585,7 @@ class Engine:
                                   dot_delta=self._dot_delta if self.fused_delta and hdt != torch.float32 else {dkey: False},
                                   fg=fg, split_ada=split_ada and not fg, gp=self.A.grad.data_ptr() if wgrads else None, dz=dz,
                                   dx=None, dmod=None, pre=None, g_send=None, g_recv=None, s_all=None)
+        self.recomputed = 0
         self._backward_final(s, dout.contiguous().float())
         proj_left = len(tp.proj)
         proj_fired = False
@@ -652,12 +702,45 @@ class Engine:
         if s.wgrads and s.pl.lora[i][lin]:
             self._lora_grads(dy, x, name, s.M, N, K, s.acc, s.dev)
 
+    def _recompute_block(self, s, i, ck):
+        """The record a saving forward leaves of block i, rebuilt from its checkpoint ck (x, y2): the forward's launches up to fc1
+        with the forward's arguments — the same kernels on the same operands, the same bits; fc2 is not run, its one saved output
+        is ck.y2.  fc1's epilogue is the one the tape's forward would have used (tp.act_grad)."""
+        tp, bf, f32 = s.tp, s.bf, s.f32
+        D, H, hd, Hm, T = self.D, self.H, self.hd, self.Hm, self.T
+        B, M, hb, Nall = s.B, s.M, s.hb, s.Nall
+        b = f"blocks.{i}."
+        mb = s.mp + hb * (i * 6 * D)
+        h, qkv, o, u = bf(M, D), bf(M, 3 * D), bf(M, D), bf(M, Hm)
+        h2, a1, y1 = bf(M, D), bf(M, Hm), bf(M, D)
+        mean1, rstd1, mean2, rstd2 = f32(M), f32(M), f32(M), f32(M)
+        lse = f32(B, H, T)
+        xmid = f32(M, D)
+        ops.ln_modulate_fwd(ck.x, mb, mb + hb * D, Nall, h, mean1, rstd1, M, D, T)
+        self._linear_fwd(b + "attn.qkv", EPI_BF16, h, M, 3 * D, D, qkv)
+        qkv_a, qstats = qkv, None
+        if self.m.qk_norm:
+            qkv_a = bf(M, 3 * D)
+            qstats = f32(M, 2, H, 2)
+            ops.qk_norm_fwd(qkv, self.Wf(b + "attn.q_norm.weight"), self.Wf(b + "attn.q_norm.bias"),
+                            self.Wf(b + "attn.k_norm.weight"), self.Wf(b + "attn.k_norm.bias"), qkv_a, qstats, M, H, hd)
+        ops.attention_fwd(qkv_a, o, lse, B, T, H, hd)
+        self._linear_fwd(b + "attn.proj", EPI_GATE_RES, o, M, D, D, xmid, C2=y1, ldc2=D, R=ck.x, ldr=D, gate=mb + 2 * hb * D,
+                         ldgate=Nall, rows_per_gate=T)
+        ops.ln_modulate_fwd(xmid, mb + 3 * hb * D, mb + 4 * hb * D, Nall, h2, mean2, rstd2, M, D, T)
+        self._linear_fwd(b + "mlp.fc1", EPI_GELU_G if tp.act_grad else EPI_GELU, h2, M, Hm, D, a1, C2=u, ldc2=Hm)
+        self.recomputed += 1
+        return types.SimpleNamespace(x=ck.x, mean1=mean1, rstd1=rstd1, h=h, qkv=qkv, qkv_a=qkv_a, qstats=qstats, o=o, lse=lse,
+                                     y1=y1, xmid=xmid, mean2=mean2, rstd2=rstd2, h2=h2, a1=a1, u=u, y2=ck.y2, rc=False)
+
     def _backward_block(self, s, i):
         """Block i's backward: stages 1 .. pl.stage[i] of freeze.py, then its adaLN rows and its gradient bucket."""
         tp, pl, bf, f32 = s.tp, s.pl, s.bf, s.f32
         D, H, hd, Hm, T = self.D, self.H, self.hd, self.Hm, self.T
         B, M, hb, Nall, dx, side = s.B, s.M, s.hb, s.Nall, s.dx, s.side
         bk = tp.blocks[i]
+        if bk.rc:   # a checkpoint (recompute.py): the full record, rebuilt now and released with the block like a saved one
+            bk = tp.blocks[i] = self._recompute_block(s, i, bk)
         b = f"blocks.{i}."
         mb = s.mp + hb * (i * 6 * D)
         last = pl.stage[i]   # the stage this block's backward stops behind

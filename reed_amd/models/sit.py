@@ -111,6 +111,11 @@ class SiT(nn.Module):
         # GEMMs (csrc/gemm_mxfp8.hip: e4m3 codes, one power-of-two scale per 32 k) wherever the kernel takes the layer's shape
         # (Engine.fp8_layers()); generate.py --sample-precision fp8.  A forward that builds a graph raises while it is set.
         self.fp8 = False
+        # activation recomputation in training (reed_amd/recompute.py): 0 / False = every block saves its activations for its
+        # backward; N = the N lowest-indexed blocks that have a backward keep their input and y2 only (6 bytes per token and channel
+        # instead of 40) and the backward rebuilds the rest with the forward's kernels — the same gradient bits; True / "all" = every
+        # such block.  Read per forward; the tape records what was kept.  train.py --recompute-blocks {N,all}.
+        self.recompute = 0
 
     # ------------------------------------------------------------------ structure
     def _param_shapes(self):

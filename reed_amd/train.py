@@ -19,7 +19,8 @@ Additive flags: --features-dirs (precomputed frozen-encoder features, §8f N2), 
 on the GPU every step from user-supplied state dicts, reed_amd/encoders.py: clip-vit-L, dinov2[reg]-vit-{s,b,l,g}, jepa-vit-h,
 mae-vit-l, mocov3-vit-{b,l}; at --resolution 512 the dinov2[reg]-vit-* towers only, at 448 pixels as the reference runs them),
 --encoder-precision {bf16,fp16,fp32,match} (the arithmetic of those towers; match = follow --mixed-precision as the reference's
-autocast does), --synthetic N (random latents), --log-every.
+autocast does), --synthetic N (random latents), --log-every, --recompute-blocks {N,all} (activation recomputation: the lowest N
+blocks keep 6 bytes per token and channel instead of 40 and are rebuilt in the backward, reed_amd/recompute.py).
 """
 import argparse
 import copy
@@ -40,7 +41,8 @@ TEXT_Z_DIM_DICT = {'text_embeds_qwenvl': 1536, 'text_embeds_open_clip': 1280, 't
 ENC_EMBED_DIM = {"s": 384, "b": 768, "l": 1024, "g": 1536, "h": 1280}  # ViT widths by model_config letter
 
 
-def parse_args(input_args=None):
+def build_parser():
+    from .recompute import parse_flag
     parser = argparse.ArgumentParser(description="Training")
     # logging:
     parser.add_argument("--output-dir", type=str, default="exps")
@@ -148,6 +150,17 @@ def parse_args(input_args=None):
     parser.add_argument("--vae-ckpt", type=str, default=None,
                         help="local sd-vae-ft checkpoint (diffusers layout): turns on the reference's preview sampling at step 1 "
                              "and every --sampling-steps (train.py:431-454), written as PNG grids under <exp>/samples/")
+    parser.add_argument("--recompute-blocks", type=parse_flag, default=0, metavar="{N,all}",
+                        help="activation recomputation (reed_amd/recompute.py): the N lowest-indexed blocks that have a backward (all: "
+                             "every one) keep their input and one 16-bit array from the forward, 6 bytes per token and channel instead "
+                             "of 40, and the backward rebuilds the rest with the forward's kernels: the same gradient bits; with all, "
+                             "on SiT-XL/2, 1.20-1.24 x the step for a peak of 33 instead of 98 GiB at local batch 256 "
+                             "(profiles/recompute.txt).  0 = off")
+    return parser
+
+
+def parse_args(input_args=None):
+    parser = build_parser()
     args = parser.parse_args(input_args) if input_args is not None else parser.parse_args()
     if args.init_from and args.resume_step > 0:
         parser.error("--init-from starts a new run at step 0; --resume-step continues one: pass one of the two")
@@ -452,17 +465,23 @@ def main(args):
         reducer = GradReducer(model, rank, world)
         reducer.broadcast_params(0)
     model.engine().save_act_grad = {"auto": None, "0": False, "1": True}[args.save_act_grad]
+    recompute = getattr(args, "recompute_blocks", 0)
     if is_main:
         eng = model.engine()
         tokens = local_batch_size * eng.T // max(1, args.gradient_accumulation_steps)
         logger.info(f"kernel forms at {tokens} tokens per GPU: activation backward "
                     f"{'saved derivative' if (eng.save_act_grad if eng.save_act_grad is not None else tokens > eng.SAVE_ACT_GRAD_MIN_TOKENS) else 'recomputed'} "
                     f"(--save-act-grad {args.save_act_grad}; auto = saved above {eng.SAVE_ACT_GRAD_MIN_TOKENS} tokens)")
+        micro = max(1, tokens // eng.T)
+        logger.info(f"saved activations at {micro} images per GPU and forward: "
+                    f"{eng.saved_activation_bytes(micro, recompute=recompute) / 2 ** 30:.3f} GiB with --recompute-blocks {recompute}, "
+                    f"{eng.saved_activation_bytes(micro, recompute=0) / 2 ** 30:.3f} GiB with 0")
     step_fn = TrainStep(model, loss_fn, optimizer, reducer, proj_coeff=args.proj_coeff,
                         repa_decay=args.repa_weight_decay, repa_steps=args.repa_steps,
                         start_diffusion_steps=args.start_diffusion_steps,
                         diffusion_warm_up_steps=args.diffusion_warm_up_steps, diffusion_decay=args.diffusion_decay,
-                        max_train_steps=args.max_train_steps, grad_accum=args.gradient_accumulation_steps)
+                        max_train_steps=args.max_train_steps, grad_accum=args.gradient_accumulation_steps,
+                        recompute=recompute)
     step_fn.global_step = global_step
     log_path = os.path.join(save_dir, "metrics.jsonl")
     t_last, n_last = time.time(), global_step

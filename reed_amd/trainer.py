@@ -58,8 +58,11 @@ class TrainStep:
     def __init__(self, model, loss_fn, optimizer, reducer=None, proj_coeff=0.5, repa_decay="constant",
                  repa_steps=400000, start_diffusion_steps=0, diffusion_warm_up_steps=50000,
                  diffusion_decay="constant", max_train_steps=400000, latents_scale=0.18215, latents_bias=0.0,
-                 grad_accum=1):
+                 grad_accum=1, recompute=None):
         self.model, self.loss_fn, self.opt, self.reducer = model, loss_fn, optimizer, reducer
+        if recompute is not None:   # --recompute-blocks: SiT.recompute (reed_amd/recompute.py); None leaves the model's setting
+            from .recompute import normalize
+            model.recompute = normalize(recompute)
         if hasattr(optimizer, "overlap") and os.environ.get("REED_OPT_OVERLAP", "1") != "0":
             optimizer.overlap = True   # the step is always followed by a forward (or by flush()/state_dict())
         self.proj_coeff = proj_coeff
